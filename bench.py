@@ -19,6 +19,16 @@ in the step; the barrier/max-over-ranks timing is the only cross-r
 call) unless it already runs under a launcher (WORLD_SIZE set, which must equal N).
 
 Prints ONE JSON line on rank 0.  value = (clips processed by all ranks / 256) / seconds.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (value,
+ms_per_step, the losses and the non-finite / range-flag counts of the timed steps).  --full adds
+everything that takes runs of its own: the per-kernel-family breakdown and the rooflines (eager
+steps under HIP events), the live gradient check, the side keys (other precisions, configs[1],
+device L-BFGS-B, the reference protocol; --side-steps) and the CPU baseline
+(--cpu-baseline-seconds).  --dump-outputs DIR writes what the last timed step left with its
+caller (rank 0's clips) as DIR/<name>.npy: parts [B, 4], grad [B, T] and the updated audio x
+[B, T], float32; the inputs are seeded per clip, so two builds run with the same arguments can
+be compared array by array.
 """
 from __future__ import annotations
 
@@ -55,8 +65,14 @@ def parse(argv=None):
     ap.add_argument('--clips', type=int, default=256, help='clips per GPU (batch)')
     ap.add_argument('--T', type=int, default=16384)
     ap.add_argument('--precision', default='split', choices=['split', 'fp32', 'bf16'])
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beside the headline figure: kernel '
+                         'breakdown and rooflines, gradient check, side keys, CPU baseline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write the last step\'s parts / grad / x as '
+                         'DIR/<name>.npy (float32; at most 64 MB in all)')
     ap.add_argument('--side-steps', type=int, default=3,
-                    help='N=1 side keys: steps of the fp32 / bf16 modes, the device L-BFGS-B mode '
+                    help='--full, N=1 side keys: steps of the fp32 / bf16 modes, the device L-BFGS-B mode '
                          'and the 1-clip configs[1] lines (0 = off)')
     ap.add_argument('--gatys', action='store_true',
                     help='configs[4]: Gatys [L,128,128] Gram instead of the channel-wise one')
@@ -68,7 +84,7 @@ def parse(argv=None):
     ap.add_argument('--graph', type=int, default=1,
                     help='1: replay the step from a captured HIP graph (default); 0: eager launches')
     ap.add_argument('--cpu-baseline-seconds', type=float, default=15.0,
-                    help='CPU baseline sample budget (0 disables)')
+                    help='--full: CPU baseline sample budget (0 disables)')
     ap.add_argument('--traffic-json', default=None,
                     help='per-launch HBM bytes measured by rocprofv3 --pmc (see DESIGN.md; default '
                          'profiles/traffic.json, profiles/traffic_gatys.json with --gatys)')
@@ -140,15 +156,42 @@ def make_problem(eng, clips, T, dev):
     return torch.tensor(x0, device=dev)
 
 
+DUMP_BUDGET = 60 * 2 ** 20      # bytes of --dump-outputs in all (under 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each [B, ...] tensor of `arrays` as path/<name>.npy in float32.  When they
+    exceed DUMP_BUDGET together, the same fixed sample of clips (rows chosen by default_rng(0),
+    in ascending order) of every array, and of a clip longer than its share the same kind of
+    sample of its columns."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    B = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    keep = max(1, min(B, DUMP_BUDGET // max(row_bytes, 1)))
+    rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    share = DUMP_BUDGET // len(arrays)      # of one clip, where a single clip exceeds the budget
+    for name, a in arrays.items():
+        a = a[rows].reshape(keep, -1)
+        if row_bytes > DUMP_BUDGET and a[0].nbytes > share:
+            cols = np.sort(np.random.default_rng(0).choice(a.shape[1], share // a.itemsize,
+                                                           replace=False))
+            a = a[:, cols]
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def run(args, Eng, precision, steps, warmup, ws, rank, dev, graph, clips=None, gatys=None,
-        groups=1):
+        groups=1, breakdown=True, dump=None):
     """Build the engine(s), warm up, time `steps` steps (barrier + sync on both sides, max over
     ranks).  A step is one AdamLoop step (ast_loss_grad + device-counter Adam), replayed from
     a captured HIP graph when `graph`; with groups > 1 one AdamGroups step (G engines of B / G
     clips, phase-shifted on G streams: every clip still takes one full step).  The per-kernel-
     family breakdown comes from HIP events of 2 extra eager steps of one engine (events are not
     recorded inside a graph).  Returns (seconds, engine timing dict, first loss, last loss,
-    (non-finite clips, range-flagged clips), clips in the timed engine)."""
+    (non-finite clips, range-flagged clips), clips in the timed engine).  breakdown=False leaves
+    the extra eager steps out (the timing dict then holds the Gram-D placement alone); dump: the
+    directory rank 0 writes the last timed step's outputs to (dump_outputs), before anything else
+    runs."""
     import torch
     from audio_style_transfer_amd.engine import AdamGroups, AdamLoop
     from audio_style_transfer_amd.shard import clip_range, max_over_ranks
@@ -185,6 +228,9 @@ def run(args, Eng, precision, steps, warmup, ws, rank, dev, graph, clips=None, g
     el = time.perf_counter() - t0
     el = max_over_ranks(el, ws, device=dev)
     last_loss = parts_of()[:, 0].mean().item()
+    if dump and rank == 0:
+        dump_outputs(dump, {'parts': parts_of(), 'grad': grad_of(),
+                            'x': torch.cat(loop.xs) if G > 1 else loop.x})
     # per-clip flag: the clip's loss parts or gradient hold a NaN / Inf (last step), and the
     # clips whose range flags (sticky over every warm-up and timed step: the loops reset them
     # at their start) report an out-of-range or non-finite evaluation
@@ -192,18 +238,20 @@ def run(args, Eng, precision, steps, warmup, ws, rank, dev, graph, clips=None, g
     bad = int((~torch.isfinite(pp).all(dim=1) | ~torch.isfinite(gg).all(dim=1)).sum().item())
     flagged = sum(int((e.range_flags() & 7).ne(0).sum().item()) for e in engs) if dev.type == 'cuda' else 0
     eng = engs[0]
-    if G > 1:
-        eng.set_cu_limit(0)   # the breakdown: one engine's kernels with every CU
-    eng.timing(True)
-    for _ in range(2):
+    tm = {}
+    if breakdown:
         if G > 1:
-            loop._front(0)
-            loop._back(0)
-        else:
-            loop._eager()
-    sync(dev)
-    tm = eng.timing_read()
-    eng.timing(False)
+            eng.set_cu_limit(0)   # the breakdown: one engine's kernels with every CU
+        eng.timing(True)
+        for _ in range(2):
+            if G > 1:
+                loop._front(0)
+                loop._back(0)
+            else:
+                loop._eager()
+        sync(dev)
+        tm = eng.timing_read()
+        eng.timing(False)
     dop = getattr(eng, 'd_out_of_place', None)
     tm['d_out_of_place'], tm['d_tuned_ms'] = dop(with_times=True) if dop else (None, None)
     del loop, xs
@@ -445,15 +493,54 @@ def gram_roofline(precision, gatys, B, T, L, fwd_ms, bwd_ms, traffic):
                         if split else 'n/a'))}
 
 
+def breakdown_keys(args, tm, Bt, ms_per_step):
+    """--full: the per-kernel-family times of run()'s eager steps (one engine: Bt = B / groups
+    clips) and the block and Gram rooflines they give, with the PMC traffic of
+    profiles/traffic.json where it was measured on this libastyle.so."""
+    B, T, L = args.clips, args.T, 30
+    calls = max(tm['calls'], 1)
+    nblk = max(tm['blocks'], 1)
+    fwd_ms = tm['block_fwd_ms'] / (calls * nblk)
+    bwd_ms = tm['block_bwd_ms'] / (calls * nblk)
+    traffic = None
+    sha = lib_sha16()
+    try:
+        tpath = args.traffic_json or os.path.join(
+            ROOT, 'profiles', 'traffic_gatys.json' if args.gatys else 'traffic.json')
+        with open(tpath) as f:
+            tj = json.load(f)
+        if (tj.get('precision') == args.precision and tj.get('clips') == Bt and tj.get('T') == T
+                and tj.get('gatys', False) == args.gatys and tj.get('lib_sha16') == sha):
+            traffic = {'fwd': tj['fwd_bytes_per_launch'], 'bwd': tj['bwd_bytes_per_launch'],
+                       'gram_fwd': tj.get('gram_fwd_bytes_per_launch'),
+                       'gram_bwd': tj.get('gram_bwd_bytes_per_launch'), 'source': tj.get('source')}
+    except Exception:
+        traffic = None
+    gram_fwd_ms = tm['gram_fwd_ms'] / calls
+    gram_bwd_ms = tm['gram_bwd_ms'] / calls
+    return {
+        'roofline': block_roofline(args.precision, Bt, T, fwd_ms, bwd_ms, traffic,
+                                   ms_per_step, gram_fwd_ms + gram_bwd_ms, B_step=B),
+        'lib_sha16': sha,
+        'kernels_ms_per_step': {'block_fwd': tm['block_fwd_ms'] / calls,
+                                'block_bwd': tm['block_bwd_ms'] / calls,
+                                'gram_fwd': gram_fwd_ms, 'gram_bwd': gram_bwd_ms,
+                                'other': tm['other_ms'] / calls},
+        'gram_roofline': gram_roofline(args.precision, args.gatys, Bt, T, L, gram_fwd_ms,
+                                       gram_bwd_ms, traffic),
+    }
+
+
 def rank_main(args):
     import torch
     ws, rank, dev = dist_setup(args)
     Eng = engine_class(args.engine)
     B, T, L = args.clips, args.T, 30
     el, tm, first_loss, last_loss, bad, Bt = run(args, Eng, args.precision, args.steps, args.warmup,
-                                                 ws, rank, dev, bool(args.graph), groups=args.groups)
+                                                 ws, rank, dev, bool(args.graph), groups=args.groups,
+                                                 breakdown=args.full, dump=args.dump_outputs)
     side = {}
-    if ws == 1 and args.side_steps > 0 and dev.type == 'cuda':
+    if args.full and ws == 1 and args.side_steps > 0 and dev.type == 'cuda':
         for p in ('fp32', 'bf16', 'split'):
             if p == args.precision:
                 continue
@@ -478,28 +565,6 @@ def rank_main(args):
         barrier(ws)
         return None
     value = ws * B * args.steps / 256.0 / el
-    calls = max(tm['calls'], 1)
-    nblk = max(tm['blocks'], 1)
-    fwd_ms = tm['block_fwd_ms'] / (calls * nblk)
-    bwd_ms = tm['block_bwd_ms'] / (calls * nblk)
-    traffic = None
-    sha = lib_sha16()
-    try:
-        tpath = args.traffic_json or os.path.join(
-            ROOT, 'profiles', 'traffic_gatys.json' if args.gatys else 'traffic.json')
-        with open(tpath) as f:
-            tj = json.load(f)
-        if (tj.get('precision') == args.precision and tj.get('clips') == Bt and tj.get('T') == T
-                and tj.get('gatys', False) == args.gatys and tj.get('lib_sha16') == sha):
-            traffic = {'fwd': tj['fwd_bytes_per_launch'], 'bwd': tj['bwd_bytes_per_launch'],
-                       'gram_fwd': tj.get('gram_fwd_bytes_per_launch'),
-                       'gram_bwd': tj.get('gram_bwd_bytes_per_launch'), 'source': tj.get('source')}
-    except Exception:
-        traffic = None
-    gram_fwd_ms = tm['gram_fwd_ms'] / calls
-    gram_bwd_ms = tm['gram_bwd_ms'] / calls
-    # the per-family breakdown is one engine's eager steps: Bt clips (B / groups)
-    gbytes = L * Bt * T * 128 * (2.0 if args.precision == 'bf16' else 4.0)
     out = {
         'metric': METRIC, 'value': value, 'unit': 'iters/s', 'n_gpus': ws, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': el / args.steps * 1e3,
@@ -518,23 +583,16 @@ def rank_main(args):
                    'gram_d_tuned_ms': tm.get('d_tuned_ms'),
                    'breakdown_engine_clips': Bt},
         'clip_iters_per_s': value * 256.0,
-        'roofline': block_roofline(args.precision, Bt, T, fwd_ms, bwd_ms, traffic,
-                                   el / args.steps * 1e3, gram_fwd_ms + gram_bwd_ms, B_step=B),
-        'lib_sha16': sha,
-        'kernels_ms_per_step': {'block_fwd': tm['block_fwd_ms'] / calls,
-                                'block_bwd': tm['block_bwd_ms'] / calls,
-                                'gram_fwd': gram_fwd_ms, 'gram_bwd': gram_bwd_ms,
-                                'other': tm['other_ms'] / calls},
-        'gram_roofline': gram_roofline(args.precision, args.gatys, Bt, T, L, gram_fwd_ms,
-                                       gram_bwd_ms, traffic),
         'loss_first_last': [first_loss, last_loss],
         'nonfinite_clips': bad[0],
         'range_flagged_clips': bad[1],
     }
-    if dev.type == 'cuda':
-        out.update(grad_check(Eng, args.precision, dev, args.gatys))
+    if args.full:
+        out.update(breakdown_keys(args, tm, Bt, el / args.steps * 1e3))
+        if dev.type == 'cuda':
+            out.update(grad_check(Eng, args.precision, dev, args.gatys))
     out.update(side)
-    if ws == 1 and args.cpu_baseline_seconds > 0:
+    if args.full and ws == 1 and args.cpu_baseline_seconds > 0:
         out['cpu_baseline'] = cpu_baseline(T, args.cpu_baseline_seconds, args.gatys)
         rp = out.get('reference_protocol')
         if rp:   # the drop-in's one-clip rate beside the CPU path's, same protocol

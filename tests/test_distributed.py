@@ -99,7 +99,9 @@ def _bench(args, env_extra=None, timeout=240):
 
 
 STUB = ['--engine', 'bench_stub:StubEngine', '--backend', 'gloo', '--T', '512', '--steps', '2',
-        '--warmup', '1', '--cpu-baseline-seconds', '0', '--side-steps', '0', '--graph', '0']
+        '--warmup', '1', '--full', '--cpu-baseline-seconds', '0', '--side-steps', '0',
+        '--graph', '0']
+PLAIN = [a for a in STUB if a != '--full']
 
 
 def test_bench_launcher_starts_ranks():
@@ -111,6 +113,52 @@ def test_bench_launcher_starts_ranks():
     assert out['n_gpus'] == 2 and out['config']['global_batch_clips'] == 6, out
     assert out['scaling'] == 'weak' and out['config']['parallelism'] == 'clip-sharded x2'
     assert out['value'] > 0 and out['nonfinite_clips'] == 0
+
+
+def test_bench_plain_run_and_dump(tmp_path):
+    """Without --full the line holds the headline figure alone (no breakdown, rooflines, gradient
+    check or baselines); --dump-outputs writes the last timed step's parts / grad / x as float32
+    .npy, the same from run to run and whether or not --full measures more afterwards."""
+    dirs = [str(tmp_path / n) for n in ('a', 'b', 'full')]
+    rc, out, err = _bench(['--gpus', '1', '--clips', '2', *PLAIN, '--dump-outputs', dirs[0]])
+    assert rc == 0, err[-2000:]
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in out, k
+    assert out['steps'] == 2 and out['ms_per_step'] > 0 and out['nonfinite_clips'] == 0
+    assert abs(out['value'] - 2 / 256.0 / (out['ms_per_step'] * 1e-3)) <= 1e-9 * out['value']
+    for k in ('roofline', 'gram_roofline', 'kernels_ms_per_step', 'grad_rel_l2', 'cpu_baseline',
+              'lbfgs_mode', 'fp32_mode'):
+        assert k not in out, k
+    rc, _, err = _bench(['--gpus', '1', '--clips', '2', *PLAIN, '--dump-outputs', dirs[1]])
+    assert rc == 0, err[-2000:]
+    rc, full, err = _bench(['--gpus', '1', '--clips', '2', *STUB, '--dump-outputs', dirs[2]])
+    assert rc == 0, err[-2000:]
+    assert 'roofline' in full and 'kernels_ms_per_step' in full
+    for name, shape in (('parts', (2, 4)), ('grad', (2, 512)), ('x', (2, 512))):
+        a = np.load(os.path.join(dirs[0], name + '.npy'))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all()
+        for d in dirs[1:]:
+            assert np.array_equal(a, np.load(os.path.join(d, name + '.npy'))), (name, d)
+    assert sorted(os.listdir(dirs[0])) == ['grad.npy', 'parts.npy', 'x.npy']
+
+
+def test_bench_dump_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """Past the byte budget the dump is the same seeded sample of clips in every array."""
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BUDGET', 4096)
+    r = np.random.default_rng(3)
+    arrs = {'parts': torch.tensor(r.normal(size=(12, 4))), 'grad': torch.tensor(r.normal(size=(12, 100)))}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrs)
+    p, g = (np.load(tmp_path / 'a' / (n + '.npy')) for n in ('parts', 'grad'))
+    assert p.dtype == g.dtype == np.float32 and p.nbytes + g.nbytes <= 4096
+    rows = [int(np.flatnonzero((arrs['parts'].float().numpy() == row).all(1))[0]) for row in p]
+    assert len(rows) == 9 and rows == sorted(set(rows))
+    assert np.array_equal(g, arrs['grad'].float().numpy()[rows])
+    assert np.array_equal(g, np.load(tmp_path / 'b' / 'grad.npy'))
+    bench.dump_outputs(str(tmp_path / 'c'), {'grad': torch.tensor(r.normal(size=(2, 5000)))})
+    c = np.load(tmp_path / 'c' / 'grad.npy')
+    assert c.shape == (1, 1024)
 
 
 def test_bench_refuses_mismatched_world_size():

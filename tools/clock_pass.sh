@@ -6,7 +6,7 @@ TAG=${1:?tag}; shift
 OUT=gpurun_out/clock_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-env "$@" timeout -s KILL 200 rocprofv3 --pmc GRBM_GUI_ACTIVE -T --output-format csv -d "$OUT" -o run -- python3 bench.py --cpu-baseline-seconds 0 --side-steps 0 > "$OUT/bench.log" 2>&1
+env "$@" timeout -s KILL 200 rocprofv3 --pmc GRBM_GUI_ACTIVE -T --output-format csv -d "$OUT" -o run -- python3 bench.py --full --cpu-baseline-seconds 0 --side-steps 0 > "$OUT/bench.log" 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 from collections import defaultdict
