@@ -295,8 +295,8 @@ static size_t d_pad() {
 
 int fused_content_occ(const ast_ctx* x);
 
-// ASTYLE_MFMA16: the split block kernels on v_mfma_f32_16x16x32_f16 (block_*_split16.hip, round 6:
-// measured): 0 = neither, 1 = forward and backward, 2 = the backward only (default:
+// ASTYLE_MFMA16: the split block kernels on v_mfma_f32_16x16x32_f16 (k_block_fwd_s16 /
+// k_block_bwd_s16; round 6: measured): 0 = neither, 1 = forward and backward, 2 = the backward only (default:
 // backward -0.3..-1.2 %, forward +4 % on 16x16x32), 3 = the forward only; read once per process, since the weight fragments are packed for the kernels that will read them
 static int mfma16_mode() {
     static int v = -1;

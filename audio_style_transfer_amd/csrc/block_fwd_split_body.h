@@ -1,62 +1,17 @@
-// ASTYLE_MFMA16=1 (round 6): the forward block kernel of block_fwd_split.hip on
-// v_mfma_f32_16x16x32_f16 fragments (splitwave.h "16x16x32"; the weights are packed for it when the
-// knob is set).  Same structure, phases and numerics class; the K accumulation order differs, so
-// results match the default kernels to fp32 rounding, not bit for bit.  Measured (DESIGN.md §3,
-// round 6): 4-5 % slower per launch than the 32x32x16 default at equal data; kept as the
-// measured alternative, not the default.
+// The forward block kernel's body (block_fwd_split.hip, which includes this file once per MFMA
+// form): the kernel SW_KERNEL on fragments of shape SW_FRAG (splitwave.h Frag32 / Frag16).  The
+// body stays inside the __global__ function: called from a wrapper it compiles to other code.
 //
-// Split-fp16 encoder block forward (precision 2): model.py:95-116 for one block,
-//   u = dconv_d(relu(e_l)) + b_d        (masked.py:110-160, K = 3, SAME zero padding)
-//   e_{l+1} = e_l + W_r^T relu(u) + b_r
-// fp32 storage, v_mfma_f32_16x16x32_f16 on split fp16 operands (round 6; 32x32x16 before), fp32
-// accumulation and fp32 epilogues (splitwave.h).
-//
-// One workgroup per CU (wave w owns output channels 32 w .. 32 w + 31), persistent over tiles
-// of 64 positions, one wave per SIMD: every epilogue runs in the shadow of MFMAs.  The two
-// 32-column halves j of a tile are separate MFMA phases, so the epilogue of one half overlaps
-// the GEMM of the other.  A tile's e_l arrives in registers (rows: unit k = image rows 8 k ..
-// 8 k + 7 x wave w's 32 channels, 8 cache lines per wave instruction), loaded during phases A
-// and B of the previous tile, and is converted into the LDS image (split relu(e_l), scaled by
-// 2^m_e from the clip's max |e_l|) and into the wave's quarter of a residual buffer (fp32 e_l,
-// double-buffered, read back by the same wave only).  Per tile i:
-//   T  barrier (image i complete)
-//   A  GEMM 1, column half 0 (3 taps x 8 k-blocks x 3 products); carries epilogue 2 of tile
-//      i-1 (8 units of 3 steps: e_i = e_{i-1} + y + b_r back into the residual rows, e > 0
-//      bits, max |e|), the flush of its half 0 (residual rows -> HBM as whole lines) and the
-//      row loads of tile i+1, units 0..4
-//   B  GEMM 1, column half 1; carries epilogue 1 of half 0 (u = acc 2^-(m_e+k_d) + b_d, u > 0
-//      bits, v = relu(u) 2^m_v -> split v image; m_v from the bound |u| <= wdn max|e_l| + bdm),
-//      the flush of epilogue 2's half 1 and the row loads of units 5..8; barrier
-//   C  GEMM 2 (8 k-blocks x 3 products), half 0; carries epilogue 1 of half 1; barrier
-//   D  GEMM 2, half 1; carries the conversion of tile i+1 (image + residual)
-// Round-2 measurements of this structure: ~13k cycles per tile against an MFMA
-// floor of 6.2k; moving the loads / conversions between phases does not change the tile time.
-// non-temporal (gfx950 CPol nt) row loads and e_{l+1} stores: every row streams through once, and
-// the stores are whole 128-B lines (round 6: -1.0 % per launch from the stores, -0.4 % from the
-// loads, profiles/r6_diag/block_ab.txt); -DSW_FWD_DEFAULT_POLICY (A/B builds) restores the default
-#ifndef SW_FWD_DEFAULT_POLICY
-#define SW_LD_AUX 2
-#define SW_ST_AUX 2
-#endif
-#include "splitwave.h"
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <type_traits>
-
-namespace ast {
-namespace {
-using namespace sw;
-
-constexpr int IROWS = 72;             // image / residual rows: 66 or 68 used, 9 units x 8 rows
-constexpr int ISLOT = IROWS * RS;     // bytes per image / residual buffer
-constexpr int LA = 2;                 // B-fragment lookahead (steps)
-
 // XIN (block 0, one-segment layout, d = 1): the rows of e_0 are recomputed from the audio
 // (e0_val: three samples per row, W0 / b0 of the lane's four channels in registers) instead of
 // loaded, so the start conv writes no e_0 tensor (model.py:82-93 folded into block 0)
+// channel of unit g / the lane's column (j, cb), inside the epilogue lambdas: formed once per unit
+// (che, ce) or at each use, as S::EARLY says (splitwave.h)
+#define SW_CH (S::EARLY ? che : ch0 + S::choff(g))
+#define SW_COL (S::EARLY ? ce : fs.col(j, cb))
 template <bool MASKED, bool ONESEG, bool XIN>
-__global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
+__global__ void __launch_bounds__(FT, 1) SW_KERNEL(FwdArgsS a, Layout) {
+    using S = SW_FRAG;
     // the layout as compile-time constants (pick_layout: one segment or masked: M = 64 with two
     // halo rows; else segments of SEGM = 32 with their pad rows), not the launch argument
     constexpr bool GEO1 = ONESEG || MASKED;
@@ -75,7 +30,7 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
     const int ntiles = a.B * tiles;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i16 = lane & 15, q4 = lane >> 4;   // 16x16x32 fragment lane (splitwave.h)
+    const S fs(lane, w);                         // the lane's fragment coordinates (splitwave.h)
     const int G = (int)gridDim.x;
     STAMP_DECL
 
@@ -101,17 +56,17 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
     pin_all(wd, wr);
     if (tid < C) { BIAS[tid] = a.bd[tid]; BIAS[C + tid] = a.br[tid]; }
 
-    // image row and time offset of the lane's column 16 cb + i16 of column half j
-    int Lc[2][2], toff[2][2];
+    // image row and time offset of the lane's column of column half j, column block cb
+    int Lc[2][S::NCB], toff[2][S::NCB];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            Lc[j][cb] = frow(32 * j + 16 * cb + i16, ly);
+        for (int cb = 0; cb < S::NCB; ++cb) {
+            Lc[j][cb] = frow(fs.col(j, cb), ly);
             toff[j][cb] = MASKED ? 0 : row_toff(Lc[j][cb], ly, a.d);
         }
-    const int chq = 32 * w + 4 * q4;  // first channel of this lane's sub-tiles (+ 16 rb)
-    const int mg0 = q4 >> 1;          // mask group of row block 0 (mgrp: + 2 rb); word h = q4 & 1
+    const int ch0 = fs.ch0();   // first channel of this lane's unit 0 (unit g: + S::choff(g))
+    const int mg0 = fs.mg0();   // mask group of unit 0 (+ S::mgoff(g))
     auto ctime = [&](const Tile& t, int cc, int to) { return col_time<MASKED>(t, cc, to, a.fn, a.d); };
 
     // ---- row units: unit k, lane -> image row L = 8 k + lr, channels cq .. cq + 3 ----
@@ -217,32 +172,35 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
     //      its quarter), and leaves for HBM from there as whole 128-B lines (flush: 8 columns x
     //      the wave's 32 channels per store); stored straight from the accumulator layout, each
     //      store would touch 32 lines 32 B at a time ----
-    f32x4 acc2[2][4];                  // y of the pending epilogue 2 (sub-tiles n = 2 cb + rb)
+    typename S::Acc acc2[2];           // y of the pending epilogue 2
     Tile prv = tile_of(blockIdx.x);
     float inv2p = 0.f;
     float emax = 0.f;
-    uint32_t mb[2][2] = {{0u, 0u}, {0u, 0u}};
+    uint32_t mb[2][S::NCB] = {};
     float4 e2e, e2b, e2o;
     auto epi2_begin = [&]() {   // (emax runs on over the workgroup's consecutive tiles of one clip)
-        mb[0][0] = mb[0][1] = mb[1][0] = mb[1][1] = 0u;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int cb = 0; cb < S::NCB; ++cb) mb[j][cb] = 0u;
     };
-    // unit u = (j, sub-tile g): channels chq + 16 rb .. + 3 of column 16 cb + i16
+    // unit u = (j, g): channels SW_CH .. + 3 of the lane's column of column block cb
     auto epi2_part = [&](int u, int part, uint8_t* erp) {
-        const int j = u >> 2, g = u & 3, rb = g & 1, cb = g >> 1;
-        const int ch = chq + 16 * rb;
+        const int j = u >> 2, g = u & 3, cb = S::cb(g);
+        const int che = S::EARLY ? ch0 + S::choff(g) : 0;
         if (part == 0) {
-            e2e = *reinterpret_cast<const float4*>(erp + Lc[j][cb] * RS + 4 * ch);
-            e2b = *reinterpret_cast<const float4*>(&BIAS[C + ch]);
+            e2e = *reinterpret_cast<const float4*>(erp + Lc[j][cb] * RS + 4 * SW_CH);
+            e2b = *reinterpret_cast<const float4*>(&BIAS[S::EARLY ? C + che : C + ch0 + S::choff(g)]);
         } else if (part == 1) {
-            e2o.x = e2e.x + fmaf(acc2[j][g][0], inv2p, e2b.x);
-            e2o.y = e2e.y + fmaf(acc2[j][g][1], inv2p, e2b.y);
-            e2o.z = e2e.z + fmaf(acc2[j][g][2], inv2p, e2b.z);
-            e2o.w = e2e.w + fmaf(acc2[j][g][3], inv2p, e2b.w);
-            *reinterpret_cast<float4*>(erp + Lc[j][cb] * RS + 4 * ch) = e2o;
+            e2o.x = e2e.x + fmaf(S::el(acc2[j], g, 0), inv2p, e2b.x);
+            e2o.y = e2e.y + fmaf(S::el(acc2[j], g, 1), inv2p, e2b.y);
+            e2o.z = e2e.z + fmaf(S::el(acc2[j], g, 2), inv2p, e2b.z);
+            e2o.w = e2e.w + fmaf(S::el(acc2[j], g, 3), inv2p, e2b.w);
+            *reinterpret_cast<float4*>(erp + Lc[j][cb] * RS + 4 * SW_CH) = e2o;
         } else {
             emax = fmaxf(emax, fmaxf(fmaxf(fabsf(e2o.x), fabsf(e2o.y)), fmaxf(fabsf(e2o.z), fabsf(e2o.w))));
-            // bit mbit(4 g' + k) = 4 k + g' of the column's word h = q4 & 1 (common.h, splitwave.h mgrp)
-            mb[j][cb] = or_pos_bits4(mb[j][cb], e2o.x, e2o.y, e2o.z, e2o.w, mg0 + 2 * rb);
+            // element k: bit 4 k + mg0 + mgoff(g) of the column's word (common.h mbit)
+            mb[j][cb] = or_pos_bits4(mb[j][cb], e2o.x, e2o.y, e2o.z, e2o.w, mg0 + S::mgoff(g));
         }
     };
     // flush piece (j, q): columns 32 j + 8 q + lr (lr = lane >> 3), channels cq .. cq + 3; part 0
@@ -262,18 +220,16 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
             bst4(mk_rsrc(a.eout + ((size_t)prv.b * a.T + prv.tb) * C), fl_lane, (uint32_t)(tu * C * 4), fl4);
         }
     };
-    // words and column times to LDS: a column's word h holds the groups of lane quads h and h + 2
-    // (the lanes 32 apart); the quads 0 / 1 write it, all four the column's time (identical values)
+    // words and column times to LDS (every lane of a column writes its time: identical values)
     auto epi2_words = [&]() {
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                const int c = 32 * j + 16 * cb + i16;
-                const uint32_t wv = mb[j][cb] | (uint32_t)__shfl_xor((int)mb[j][cb], 32);
-                if (q4 < 2) MBE[c * 8 + 4 * q4 + w] = (uint16_t)wv;
-                MBT[c] = ctime(prv, c, toff[j][cb]);
-            }
+        for (int q = 0; q < 2 * S::NCB; ++q) {   // (one loop: nested, the one-block form compiles to other code)
+            const int j = q / S::NCB, cb = q % S::NCB;
+            const int c = fs.col(j, cb);
+            const uint32_t wv = fs.col_word(mb[j][cb]);
+            if (S::ALL_WRITE || fs.lk < 2) MBE[c * 8 + 4 * fs.lk + w] = (uint16_t)wv;
+            MBT[c] = ctime(prv, c, toff[j][cb]);
+        }
     };
     // max |e_{l+1}| of clip prv.b -> gmax_out, once per run of tiles of one clip (with the
     // clip-interleaved tile order a workgroup usually keeps its clip for the whole launch)
@@ -287,41 +243,40 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
     // v = relu(u) 2^m_v = relu(acc 2^(m_v - m_e - k_d) + b_d 2^m_v): the scale folded into the fma
     // (powers of two: the same values); the u > 0 bits from the split's rtz hi halves (splitwave.h
     // nz2; SW_UBITS_EXACT: from v itself)
-    f32x4 acc1[2][4];
+    typename S::Acc acc1[2];
     float a1 = 0.f;
     float bs_sv = -1.f;   // the v scale BDS holds
     uint32_t mu_w = 0;
     float4 e1v;
-    // sub-tile g of column half j (rb = g & 1, cb = g >> 1); after both row blocks of a column
-    // block the column's u > 0 word (the other two groups from the lane quad q4 ^ 2)
+    // unit g of column half j; after the last unit of a column its u > 0 word
     auto epi1_part = [&](int j, int g, int part) {
-        const int rb = g & 1, cb = g >> 1, ch = chq + 16 * rb;
+        const int cb = S::cb(g), che = S::EARLY ? ch0 + S::choff(g) : 0;
         if (part == 0) {
-            const float4 b4 = *reinterpret_cast<const float4*>(&BDS[ch]);
-            e1v.x = fmaxf(fmaf(acc1[j][g][0], a1, b4.x), 0.f);
-            e1v.y = fmaxf(fmaf(acc1[j][g][1], a1, b4.y), 0.f);
-            e1v.z = fmaxf(fmaf(acc1[j][g][2], a1, b4.z), 0.f);
-            e1v.w = fmaxf(fmaf(acc1[j][g][3], a1, b4.w), 0.f);
+            const float4 b4 = *reinterpret_cast<const float4*>(&BDS[SW_CH]);
+            e1v.x = fmaxf(fmaf(S::el(acc1[j], g, 0), a1, b4.x), 0.f);
+            e1v.y = fmaxf(fmaf(S::el(acc1[j], g, 1), a1, b4.y), 0.f);
+            e1v.z = fmaxf(fmaf(S::el(acc1[j], g, 2), a1, b4.z), 0.f);
+            e1v.w = fmaxf(fmaf(S::el(acc1[j], g, 3), a1, b4.w), 0.f);
         } else {
             uint32_t h01, l01, h23, l23;
             split2(e1v.x, e1v.y, h01, l01);
             split2(e1v.z, e1v.w, h23, l23);
-            const int c = 32 * j + 16 * cb + i16;
-            uint8_t* p = XV + c * RS + 2 * ch;
+            const int ce = S::EARLY ? fs.col(j, cb) : 0;
+            uint8_t* p = XV + SW_COL * RS + 2 * SW_CH;
             *reinterpret_cast<uint2*>(p) = make_uint2(h01, h23);
             *reinterpret_cast<uint2*>(p + 256) = make_uint2(l01, l23);
 #ifdef SW_UBITS_EXACT
-            mu_w = or_pos_bits4(mu_w, e1v.x, e1v.y, e1v.z, e1v.w, mg0 + 2 * rb);
-            if (rb == 1) {
-                const uint32_t wv = mu_w | (uint32_t)__shfl_xor((int)mu_w, 32);
-                if (q4 < 2) MBU[c * 8 + 4 * q4 + w] = (uint16_t)wv;
+            mu_w = or_pos_bits4(mu_w, e1v.x, e1v.y, e1v.z, e1v.w, mg0 + S::mgoff(g));
+            if (S::col_done(g)) {
+                const uint32_t wv = fs.col_word(mu_w);
+                if (S::ALL_WRITE || fs.lk < 2) MBU[SW_COL * 8 + 4 * fs.lk + w] = (uint16_t)wv;
                 mu_w = 0;
             }
 #else
-            mu_w = or_bits4(mu_w, h01, h23, mg0 + 2 * rb);
-            if (rb == 1) {
-                const uint32_t wv = mask16(mu_w | (uint32_t)__shfl_xor((int)mu_w, 32));
-                if (q4 < 2) MBU[c * 8 + 4 * q4 + w] = (uint16_t)wv;
+            mu_w = or_bits4(mu_w, h01, h23, mg0 + S::mgoff(g));
+            if (S::col_done(g)) {
+                const uint32_t wv = mask16(fs.col_word(mu_w));
+                if (S::ALL_WRITE || fs.lk < 2) MBU[SW_COL * 8 + 4 * fs.lk + w] = (uint16_t)wv;
                 mu_w = 0;
             }
 #endif
@@ -329,29 +284,29 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
     };
 
 
-    // ---- GEMM 1 of column half J over the image; side work per step.  Step st = (tap, K block
-    //      kb of 32, column block cb): 3 split products x 2 row blocks (splitwave.h) ----
+    // ---- GEMM 1 of column half J over the image; side work per step.  Step st = (tap st >> 3,
+    //      step st & 7 of the tap's K pass: S::skb, S::scb) ----
     auto gemm1h = [&](auto j_tag, auto side, const Tile& cu) {
         constexpr int J = decltype(j_tag)::value;
-        bool ok0[2] = {true, true}, ok2[2] = {true, true};
+        bool ok0[S::NCB], ok2[S::NCB];
+#pragma unroll
+        for (int cb = 0; cb < S::NCB; ++cb) ok0[cb] = ok2[cb] = true;
         if (MASKED) {
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                const int pc = cu.p0 + 32 * J + 16 * cb + i16;
+            for (int cb = 0; cb < S::NCB; ++cb) {
+                const int pc = cu.p0 + fs.col(J, cb);
                 const int m = pc - (int)fdiv((uint32_t)pc, a.fn) * a.n;
                 ok0[cb] = m > 0;
                 ok2[cb] = m < a.n - 1;
             }
         }
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc1[J][n][i] = 0.f;
-        // B fragments are read LA steps ahead (one step ahead leaves the LDS latency exposed)
+        S::zero(acc1[J]);
+        // B fragments are read LA steps ahead (a 32x32x16 step is only 3 MFMAs: one step ahead
+        // leaves the LDS latency exposed)
         uint4 bh[LA + 1], bl[LA + 1];
         auto bread = [&](int st, uint4& xh, uint4& xl) {
-            const int tp = st >> 3, kb = (st & 7) >> 1, cb = st & 1;
-            const uint8_t* p = IMG + (Lc[J][cb] + tp - 1) * RS + kb * 64 + q4 * 16;
+            const int tp = st >> 3, s = st & 7;
+            const uint8_t* p = fs.bfrag(IMG + (Lc[J][S::scb(s)] + tp - 1) * RS, S::skb(s));
             xh = lds16(p);
             xl = lds16(p + 256);
         };
@@ -359,36 +314,25 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
         for (int q = 0; q < LA; ++q) bread(q, bh[q], bl[q]);
 #pragma unroll
         for (int st = 0; st < 24; ++st) {
-            const int tp = st >> 3, kb = (st & 7) >> 1, cb = st & 1, bi = st % (LA + 1);
+            const int tp = st >> 3, s = st & 7, cb = S::scb(s), bi = st % (LA + 1);
             uint4 xh = bh[bi], xl = bl[bi];
             if (MASKED && ((tp == 0 && !ok0[cb]) || (tp == 2 && !ok2[cb]))) {
                 xh = make_uint4(0, 0, 0, 0);
                 xl = xh;
             }
-            f32x4& c0 = acc1[J][2 * cb];
-            f32x4& c1 = acc1[J][2 * cb + 1];
-            c0 = mfma16(wd[tp][2 * kb][0], xh, c0);
-            c1 = mfma16(wd[tp][2 * kb + 1][0], xh, c1);
+            S::step_first(acc1[J], wd[tp], S::skb(s), cb, xh);
             if (st + LA < 24) bread(st + LA, bh[(st + LA) % (LA + 1)], bl[(st + LA) % (LA + 1)]);
             side(st);
-            c0 = mfma16(wd[tp][2 * kb][1], xh, c0);
-            c1 = mfma16(wd[tp][2 * kb + 1][1], xh, c1);
-            c0 = mfma16(wd[tp][2 * kb][0], xl, c0);
-            c1 = mfma16(wd[tp][2 * kb + 1][0], xl, c1);
-            step6_schedule();
+            S::step_rest(acc1[J], wd[tp], S::skb(s), cb, xh, xl);
         }
     };
-    // ---- GEMM 2 of column half J over the v image; step st = (K block st >> 1, column block
-    //      st & 1) ----
+    // ---- GEMM 2 of column half J over the v image: one K pass ----
     auto gemm2h = [&](auto j_tag, auto side) {
         constexpr int J = decltype(j_tag)::value;
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc2[J][n][i] = 0.f;
+        S::zero(acc2[J]);
         uint4 bh[LA + 1], bl[LA + 1];
         auto bload = [&](int st, uint4& xh, uint4& xl) {
-            const uint8_t* p = XV + (32 * J + 16 * (st & 1) + i16) * RS + (st >> 1) * 64 + q4 * 16;
+            const uint8_t* p = fs.bfrag(XV + fs.col(J, S::scb(st)) * RS, S::skb(st));
             xh = lds16(p);
             xl = lds16(p + 256);
         };
@@ -396,18 +340,11 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
         for (int q = 0; q < LA; ++q) bload(q, bh[q], bl[q]);
 #pragma unroll
         for (int st = 0; st < 8; ++st) {
-            const int kb = st >> 1, cb = st & 1, bi = st % (LA + 1);
-            f32x4& c0 = acc2[J][2 * cb];
-            f32x4& c1 = acc2[J][2 * cb + 1];
-            c0 = mfma16(wr[2 * kb][0], bh[bi], c0);
-            c1 = mfma16(wr[2 * kb + 1][0], bh[bi], c1);
+            const int bi = st % (LA + 1);
+            S::step_first(acc2[J], wr, S::skb(st), S::scb(st), bh[bi]);
             if (st + LA < 8) bload(st + LA, bh[(st + LA) % (LA + 1)], bl[(st + LA) % (LA + 1)]);
             side(st);
-            c0 = mfma16(wr[2 * kb][1], bh[bi], c0);
-            c1 = mfma16(wr[2 * kb + 1][1], bh[bi], c1);
-            c0 = mfma16(wr[2 * kb][0], bl[bi], c0);
-            c1 = mfma16(wr[2 * kb + 1][0], bl[bi], c1);
-            step6_schedule();
+            S::step_rest(acc2[J], wr, S::skb(st), S::scb(st), bh[bi], bl[bi]);
         }
     };
     using J0 = std::integral_constant<int, 0>;
@@ -517,22 +454,5 @@ __global__ void __launch_bounds__(FT, 1) k_block_fwd_s16(FwdArgsS a, Layout) {
     STAMP(4)
     STAMP_FLUSH(a.stamps)
 }
-
-}  // namespace
-
-void launch_block_fwd_s16(const FwdArgsS& a0, hipStream_t s) {
-    FwdArgsS a = a0;
-    a.fn = make_fdiv((uint32_t)a.n);
-    a.ft = make_fdiv((uint32_t)(SW_TILE_INTERLEAVE ? a.B : a.T / TMS));
-    const int nt = a.B * (a.T / TMS);
-    const dim3 grid(std::min(nt, a.cus > 0 ? std::min(a.cus, sw::num_cus()) : sw::num_cus()));
-    Layout ly;
-    const bool masked = pick_layout(a.n, ly);
-    if (a.xin && (masked || ly.M != TMS || a.d != 1)) { fprintf(stderr, "block_fwd_s: xin needs d = 1\n"); abort(); }
-    if (masked) hipLaunchKernelGGL((k_block_fwd_s16<true, false, false>), grid, dim3(FT), 0, s, a, ly);
-    else if (ly.M == TMS && a.xin) hipLaunchKernelGGL((k_block_fwd_s16<false, true, true>), grid, dim3(FT), 0, s, a, ly);
-    else if (ly.M == TMS) hipLaunchKernelGGL((k_block_fwd_s16<false, true, false>), grid, dim3(FT), 0, s, a, ly);
-    else hipLaunchKernelGGL((k_block_fwd_s16<false, false, false>), grid, dim3(FT), 0, s, a, ly);
-}
-
-}  // namespace ast
+#undef SW_CH
+#undef SW_COL

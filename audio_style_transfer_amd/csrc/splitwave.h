@@ -244,24 +244,16 @@ __device__ __forceinline__ int scale_exp(float mx) {
 }
 __device__ __forceinline__ float exp2i(int e) { return __builtin_ldexpf(1.0f, e); }
 
-// split four fp32 values (already scaled) into rtz fp16 halves: hi / lo as 2 dwords each
-__device__ __forceinline__ void split4(float a0, float a1, float a2, float a3, uint2& hi, uint2& lo) {
-    const auto h01 = __builtin_amdgcn_cvt_pkrtz(a0, a1);
-    const auto h23 = __builtin_amdgcn_cvt_pkrtz(a2, a3);
-    const auto l01 = __builtin_amdgcn_cvt_pkrtz(a0 - (float)h01[0], a1 - (float)h01[1]);
-    const auto l23 = __builtin_amdgcn_cvt_pkrtz(a2 - (float)h23[0], a3 - (float)h23[1]);
-    hi = make_uint2(__builtin_bit_cast(uint32_t, h01), __builtin_bit_cast(uint32_t, h23));
-    lo = make_uint2(__builtin_bit_cast(uint32_t, l01), __builtin_bit_cast(uint32_t, l23));
-}
-
 __device__ __forceinline__ f32x16 mfma_f16(uint4 a, uint4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a),
                                                    __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-// ---- the 16x16x32 form (ASTYLE_MFMA16=1: block_fwd_split16.hip, block_bwd_split16.hip; round 6,
-//      measured no faster than the 32x32x16 default).  A wave's output tile of a
-//      column half is its 32 channels x 32 columns as four 16 x 16 sub-tiles n = 2 cb + rb (row
+// ---- the 16x16x32 form (k_block_fwd_s16 in block_fwd_split.hip, k_block_bwd_s16 in
+//      block_bwd_split16.hip; ASTYLE_MFMA16 picks the form per direction; shipped, mode 2: the
+//      backward runs on it, 0.3-1.2 % faster per launch than on 32x32x16, the forward stays on
+//      32x32x16, where 16x16x32 is 4-5 % slower; round 6).  A wave's output tile of
+//      a column half is its 32 channels x 32 columns as four 16 x 16 sub-tiles n = 2 cb + rb (row
 //      block rb: channels 16 rb .. + 15 of the wave's 32; column block cb: columns 16 cb .. + 15).
 //      Lane (i = lane & 15, q = lane >> 4):
 //        A fragment (weights, slot s = 2 kb + rb of K block kb of 32): A[16 rb + i][32 kb + 8 q + e]
@@ -287,6 +279,101 @@ __device__ __forceinline__ void step6_schedule() {
     __builtin_amdgcn_sched_barrier(0);
 }
 
+// folds a mask accumulator of or_bits4 (below) into the u16 mask-word layout
+__device__ __forceinline__ uint32_t mask16(uint32_t w) { return (w | (w >> 12)) & 0xffffu; }
+
+// ---- fragment shapes: what a block kernel body written once for both MFMA forms
+//      (block_fwd_split_body.h) needs to know about the form.  A wave's output of a column half
+//      (its 32 channels x 32 columns) is NCB column blocks; a lane holds, per column half, four
+//      units g of 4 consecutive channels of one column (element k of unit g: column col(j, cb(g)),
+//      channel ch0() + choff(g) + k, bit 4 k + mg0() + mgoff(g) of the column's mask word,
+//      common.h mbit).  A K pass over the 128 input channels is 8 steps s = (K block skb(s),
+//      column block scb(s)) of one B fragment pair each.
+//      The members are shaped by what the compiler makes of them, not only by taste: the body
+//      must compile to the code of the kernels it replaced (tools/diag/isa_compare.py), and that
+//      depends on where a value is formed (ch0 / mg0: in the body, after its column setup) and
+//      on how an address is associated (bfrag: pointer steps, not one summed offset). ----
+struct Frag32 {   // v_mfma_f32_32x32x16_f16: lane = (lc = lane & 31, lk = lane >> 5)
+    typedef f32x16 Acc;   // unit g: elements 4 g .. 4 g + 3 = channels 8 g + 4 lk .. + 3
+    static constexpr int NCB = 1;
+    const int lc, lk, w;
+    __device__ __forceinline__ Frag32(int lane, int w_) : lc(lane & 31), lk(lane >> 5), w(w_) {}
+    __device__ __forceinline__ int col(int j, int) const { return 32 * j + lc; }   // tile column
+    static __device__ __forceinline__ int cb(int) { return 0; }                    // column block of unit g
+    __device__ __forceinline__ int ch0() const { return 32 * w + 4 * lk; }         // unit g: channels ch0 + choff(g) ..
+    static __device__ __forceinline__ int choff(int g) { return 8 * g; }
+    // the body forms a unit's channel and column at each use (Frag16: once per unit), as the
+    // kernel of each form did when it was tuned: the compiled code depends on it
+    static constexpr bool EARLY = false;
+    __device__ __forceinline__ int mg0() const { return 0; }                       //         mask group mg0 + mgoff(g)
+    static __device__ __forceinline__ int mgoff(int g) { return g; }
+    static __device__ __forceinline__ bool col_done(int g) { return g == 3; }     // last unit of its column
+    static __device__ __forceinline__ float el(const Acc& a, int g, int k) { return a[4 * g + k]; }
+    static __device__ __forceinline__ void zero(Acc& a) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = 0.f;
+    }
+    static __device__ __forceinline__ int skb(int s) { return s; }   // step s: K block of 16
+    static __device__ __forceinline__ int scb(int) { return 0; }     //         column block
+    // B fragment of K block kb in an image row
+    __device__ __forceinline__ const uint8_t* bfrag(const uint8_t* row, int kb) const { return row + kb * 32 + lk * 16; }
+    // one step in two parts, the next B reads and the side work between them: the first of the 3
+    // split products, then the other two
+    static __device__ __forceinline__ void step_first(Acc& acc, const uint4 (&wf)[8][2], int kb, int, uint4 xh) {
+        acc = mfma_f16(wf[kb][0], xh, acc);
+    }
+    static __device__ __forceinline__ void step_rest(Acc& acc, const uint4 (&wf)[8][2], int kb, int, uint4 xh, uint4 xl) {
+        acc = mfma_f16(wf[kb][1], xh, acc);
+        acc = mfma_f16(wf[kb][0], xl, acc);
+        step3_schedule();
+    }
+    // a column's 8 u16 mask words: the lane holds all four groups of word 4 lk + w of its column
+    __device__ __forceinline__ uint32_t col_word(uint32_t m) const { return m; }   // the finished word
+    static constexpr bool ALL_WRITE = true;   // every lane writes its word
+};
+struct Frag16 {   // v_mfma_f32_16x16x32_f16 (above): lane = (lc = lane & 15, lk = lane >> 4)
+    typedef f32x4 Acc[4];   // unit g = sub-tile 2 cb + rb: channels 16 rb + 4 lk .. + 3
+    static constexpr int NCB = 2;
+    const int lc, lk, w;
+    __device__ __forceinline__ Frag16(int lane, int w_) : lc(lane & 15), lk(lane >> 4), w(w_) {}
+    __device__ __forceinline__ int col(int j, int cb_) const { return 32 * j + 16 * cb_ + lc; }
+    static __device__ __forceinline__ int cb(int g) { return g >> 1; }
+    __device__ __forceinline__ int ch0() const { return 32 * w + 4 * lk; }
+    static __device__ __forceinline__ int choff(int g) { return 16 * (g & 1); }
+    static constexpr bool EARLY = true;
+    __device__ __forceinline__ int mg0() const { return lk >> 1; }
+    static __device__ __forceinline__ int mgoff(int g) { return 2 * (g & 1); }
+    static __device__ __forceinline__ bool col_done(int g) { return (g & 1) == 1; }
+    static __device__ __forceinline__ float el(const Acc& a, int g, int k) { return a[g][k]; }
+    static __device__ __forceinline__ void zero(Acc& a) {
+#pragma unroll
+        for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[n][i] = 0.f;
+    }
+    static __device__ __forceinline__ int skb(int s) { return s >> 1; }   // step s: K block of 32
+    static __device__ __forceinline__ int scb(int s) { return s & 1; }
+    __device__ __forceinline__ const uint8_t* bfrag(const uint8_t* row, int kb) const { return row + kb * 64 + lk * 16; }
+    // 3 products x 2 row blocks (weight slots 2 kb, 2 kb + 1)
+    static __device__ __forceinline__ void step_first(Acc& acc, const uint4 (&wf)[8][2], int kb, int cb_, uint4 xh) {
+        acc[2 * cb_] = mfma16(wf[2 * kb][0], xh, acc[2 * cb_]);
+        acc[2 * cb_ + 1] = mfma16(wf[2 * kb + 1][0], xh, acc[2 * cb_ + 1]);
+    }
+    static __device__ __forceinline__ void step_rest(Acc& acc, const uint4 (&wf)[8][2], int kb, int cb_, uint4 xh, uint4 xl) {
+        f32x4& c0 = acc[2 * cb_];
+        f32x4& c1 = acc[2 * cb_ + 1];
+        c0 = mfma16(wf[2 * kb][1], xh, c0);
+        c1 = mfma16(wf[2 * kb + 1][1], xh, c1);
+        c0 = mfma16(wf[2 * kb][0], xl, c0);
+        c1 = mfma16(wf[2 * kb + 1][0], xl, c1);
+        step6_schedule();
+    }
+    // a column's word lk & 1 holds the groups of the lane quads lk and lk ^ 2 (the lanes 32
+    // apart); the quads 0 / 1 write it
+    __device__ __forceinline__ uint32_t col_word(const uint32_t& m) const { return m | (uint32_t)__shfl_xor((int)m, 32); }
+    static constexpr bool ALL_WRITE = false;  // the lane quads lk < 2 write the words 4 lk + w
+};
+
 // tied no-op: pins a fragment to the accumulator register file (MFMA A operands may be AGPRs)
 __device__ __forceinline__ uint4 to_agpr(uint4 v) {
     u32x4 t = __builtin_bit_cast(u32x4, v);
@@ -301,7 +388,7 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// scalar load of a uniform word: a compiler-visible vector load would make the compiler wait
+// scalar loads of uniform words (sload_gmax): a compiler-visible vector load would make the compiler wait
 // for every older vector-memory op, the kernels' in-flight DMA included.  The words it reads are
 // per-clip maxima that atomics of the PREVIOUS launch on the same stream wrote: the kernel
 // boundary (the producer's end-of-kernel release, this kernel's start acquire, which invalidates
@@ -309,12 +396,7 @@ __device__ __forceinline__ void lds_barrier() {
 // cache on every load): no change to the graph-replay defect of DESIGN.md §3, and +1.3 ms per
 // step at one clip, where every workgroup of a launch reads the same word (configs[1]: 478 ->
 // 299 iters/s); reverted
-__device__ __forceinline__ float sload(const float* p) {
-    float v;
-    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p) : "memory");
-    return v;
-}
-
+//
 // a clip's max over its GSLOTS slots (common.h): eight scalar loads in flight, one wait.  The
 // outputs are early-clobber: a load's destination must not be the base pair the later loads read
 __device__ __forceinline__ float sload_gmax(const float* lvl, int b) {
@@ -438,7 +520,6 @@ __device__ __forceinline__ uint32_t or_bits4(uint32_t w, uint32_t hi01, uint32_t
         : "=&v"(t0), "=&v"(t1) : "v"(hi01), "v"(hi23), "s"(0x00010001u));
     return (t0 << g) | w;
 }
-__device__ __forceinline__ uint32_t mask16(uint32_t w) { return (w | (w >> 12)) & 0xffffu; }
 
 }  // namespace sw
 }  // namespace ast
