@@ -137,6 +137,12 @@ struct ast_ctx {
     float2* stft_tw = nullptr;              // STFT regulariser: twiddles [1024]
     float* stft_fpart = nullptr;            //   per-frame partial sums [B][nf]
     float* stft_gfr = nullptr;              //   per-frame gradients [B][nf][1024]
+    const float* anc_ref = nullptr;         // seam anchor term (ast_set_anchor): caller's ref [B][T],
+    const float* anc_w = nullptr;           //   caller's weights [B][T]; anc_ref == null: term unset
+    float anc_mu = 0.f;
+    float* anc_part = nullptr;              //   chunk partials [B][anchor_chunks(T)][2]
+    float* anc_loss = nullptr;              //   the term's value per clip at the last evaluation [B]
+    bool anc_evaluated = false;             //   anc_loss holds an evaluation of the current setting
     std::vector<const void*> lb_ws;         // workspaces started here with x0 (ast_lbfgs_begin)
     void* zero = nullptr;                   // 256 zero bytes
     int* rflags = nullptr;                  // [B] AST_RANGE_* OR'ed over ast_loss_grad calls since the last reset
@@ -342,6 +348,7 @@ size_t workspace_bytes(const ast_cfg* c, const ast_ctx* x) {
     n += (size_t)c->batch * x->occ.size() * (c->T / CROWS) * 4;
     const int nf = stft_frames(c->T);
     if (nf) n += 1024 * 8 + (size_t)c->batch * nf * (1 + 1024) * 4;   // STFT regulariser
+    n += (size_t)c->batch * (2 * anchor_chunks(c->T) + 1) * 4;        // seam anchor partials, values
     return n;
 }
 
@@ -808,6 +815,8 @@ int ast_create(const ast_cfg* cfg, int hip_device, ast_ctx** out) {
         e = hipDeviceSynchronize();
         if (e != hipSuccess) { ast_destroy(x); return fail(AST_E_HIP, hipGetErrorString(e)); }
     }
+    ALLOC(x->anc_part, (size_t)c.batch * anchor_chunks(c.T) * 2 * 4);
+    ALLOC(x->anc_loss, (size_t)c.batch * 4);
 #undef ALLOC
     x->doop_tune = doop_env() < 0 && x->dgrad &&
                    (size_t)(x->nblk + 1) * x->tstride * x->esz >= ((size_t)4 << 30);
@@ -1047,6 +1056,44 @@ int ast_set_gamma(ast_ctx* x, float gamma) {
     return 0;
 }
 
+int ast_set_anchor(ast_ctx* x, const float* ref, const float* w, float mu) {
+    if (!x) return fail(AST_E_ARG, "null argument");
+    if (!(mu >= 0.f) || !std::isfinite(mu)) return fail(AST_E_ARG, "ast_set_anchor: mu must be finite and >= 0");
+    if (ref && mu != 0.f && !w) return fail(AST_E_ARG, "ast_set_anchor: ref without weights");
+    const bool on = ref && mu != 0.f;
+    x->anc_ref = on ? ref : nullptr;
+    x->anc_w = on ? w : nullptr;
+    x->anc_mu = on ? mu : 0.f;
+    x->anc_evaluated = false;
+    x->lg_front_done = false;
+    return 0;
+}
+
+int ast_anchor_loss(ast_ctx* x, float* out, void* stream) {
+    if (!x || !out) return fail(AST_E_ARG, "null argument");
+    const size_t nb = (size_t)x->cfg.batch * 4;
+    if (x->anc_ref && x->anc_evaluated)
+        HIPCHK(hipMemcpyAsync(out, x->anc_loss, nb, hipMemcpyDeviceToDevice, S(stream)));
+    else
+        HIPCHK(hipMemsetAsync(out, 0, nb, S(stream)));
+    return 0;
+}
+
+int ast_stitch(const float* xd, int n, int T, int late, int fade, float* out, void* stream) {
+    if (!xd || !out) return fail(AST_E_ARG, "null argument");
+    if (n < 1) return fail(AST_E_ARG, "ast_stitch: need n >= 1 windows");
+    if (T < 4096) return fail(AST_E_ARG, "ast_stitch: T must be >= 4096 (no sample survives the guard)");
+    if (late < 0 || 2 * (long long)late >= T) return fail(AST_E_ARG, "ast_stitch: need 0 <= 2 late < T");
+    if (fade < 0) return fail(AST_E_ARG, "ast_stitch: fade must be >= 0");
+    if (2 * (long long)fade > T - 2 * late)
+        return fail(AST_E_ARG, "ast_stitch: 2 fade must be <= T - 2 late (a window's fades would meet)");
+    const long long n_out = (long long)(n - 1) * (T - 2 * late - fade) + T - 2 * late;
+    if ((n_out + 255) / 256 > 0x7fffffffll) return fail(AST_E_ARG, "ast_stitch: output too long");
+    launch_stitch(xd, out, n, T, late, fade, S(stream));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // ast_loss_grad in two phases (ast_loss_grad_phase): the front runs the encoder forward, the
 // content taps and the Gram forward / style loss / Gram backward; the back runs the backward
 // chain through the blocks, d loss / d x, the loss parts, the STFT regulariser and the flags.
@@ -1231,6 +1278,12 @@ static int loss_grad_back(ast_ctx* x, const float* xd, float* grad, float* parts
     // always holds it; its gradient enters grad only through gamma
     launch_stft_reg(xd, x->stft_tw, x->stft_fpart, x->stft_gfr, grad, parts, c.gamma, c.batch,
                     c.T, s);
+    // seam anchor term (ast_set_anchor): nothing launches while it is unset
+    if (x->anc_ref) {
+        launch_anchor(xd, x->anc_ref, x->anc_w, x->anc_part, grad, parts, x->anc_loss, x->anc_mu,
+                      c.batch, c.T, s);
+        x->anc_evaluated = true;
+    }
     {
         RangeArgs ra;
         memset(&ra, 0, sizeof(ra));

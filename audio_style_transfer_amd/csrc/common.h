@@ -402,6 +402,14 @@ void launch_stft_twiddles(float2* tw, hipStream_t s);
 void launch_stft_reg(const float* x, const float2* tw, float* fpart, float* gfr, float* grad,
                      float* parts, float gamma, int B, int T, hipStream_t s);
 
+// seam anchor term (anchor.hip, no reference counterpart): chunk partials [B][anchor_chunks][2]
+int anchor_chunks(int T);
+void launch_anchor(const float* x, const float* ref, const float* w, float* part, float* grad,
+                   float* parts, float* aloss, float mu, int B, int T, hipStream_t s);
+
+// join of overlapping windows (stitch.hip, no reference counterpart)
+void launch_stitch(const float* x, float* out, int n, int T, int late, int fade, hipStream_t s);
+
 // batched device L-BFGS-B (lbfgs.hip, methods.py:132-137)
 size_t lbfgs_workspace_bytes(int B, int T, int m);
 void launch_lbfgs_begin(void* ws, float* x, const double* x0, const int* active, int B, int T,

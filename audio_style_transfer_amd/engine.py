@@ -48,7 +48,8 @@ class StyleEngine:
         self.cnt_channels = int(cnt_channels)
         self.lambd = float(lambd)
         self.gamma = float(gamma)
-        self.gen = 0    # bumped by every setting a captured graph bakes in (set_gamma)
+        self.gen = 0    # bumped by every setting a captured graph bakes in (set_gamma, set_anchor)
+        self._anchor = None
         cfg = _lib.AstCfg()
         cfg.batch, cfg.T = self.batch, self.T
         cfg.n_cont = len(self.cont_ids)
@@ -180,6 +181,31 @@ class StyleEngine:
         self.gamma = float(gamma)
         self.gen += 1   # captured graphs hold launch parameters derived from gamma: recapture
 
+    def set_anchor(self, ref: Optional[torch.Tensor], w: Optional[torch.Tensor] = None,
+                   mu: float = 0.0) -> None:
+        """The seam anchor term (ast_set_anchor): mu * sum_t w (inv_mu_law(x) - ref)^2 / sum_t w
+        per clip, added to parts[:, 0] and the gradient of every loss_grad.  ref [B, T] (audio
+        units) and w [B, T] (>= 0) are float32 tensors on the engine's device, used as they are
+        and kept alive here: their values may be overwritten in place between evaluations.
+        ``ref=None`` (or mu == 0) clears the term."""
+        if ref is None or float(mu) == 0.0:
+            _lib.check(self.lib.ast_set_anchor(self.h, None, None, 0.0))
+            self._anchor = None
+        else:
+            for t in (ref, w):
+                if t is None or tuple(t.shape) != (self.batch, self.T):
+                    raise ValueError('anchor ref and w must be [%d, %d]' % (self.batch, self.T))
+            _lib.check(self.lib.ast_set_anchor(self.h, self._ptr(ref), self._ptr(w), float(mu)))
+            self._anchor = (ref, w)          # keep alive: the context holds raw pointers
+        self.gen += 1   # the term's kernels launch only while it is set: recapture
+
+    def anchor_loss(self) -> torch.Tensor:
+        """The anchor term's value per clip [B] (mu included) at the most recent loss_grad; 0
+        while the term is unset."""
+        out = torch.empty(self.batch, device=self.device)
+        _lib.check(self.lib.ast_anchor_loss(self.h, self._ptr(out), self._stream()))
+        return out
+
     def loss_grad(self, x: torch.Tensor, grad: Optional[torch.Tensor] = None,
                   parts: Optional[torch.Tensor] = None):
         """Returns (parts [B, 4] = (total, content, style, reg), grad [B, T]).  reg is the STFT
@@ -257,6 +283,26 @@ class StyleEngine:
         return dict(zip(keys, list(out)))
 
 
+def stitch(x: torch.Tensor, late: int, fade: int) -> torch.Tensor:
+    """ast_stitch: join the windows x [n, T] (float32 mu-law units on a GPU, window k starting
+    hop = T - 2 late - fade samples after window k - 1) into one audio signal
+    [(n - 1) hop + T - 2 late]: the guards dropped, neighbours crossfaded over ``fade`` samples
+    (longform.geometry).  Not peak-normalised."""
+    if x.dim() != 2 or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError('stitch needs a float32 [n, T] tensor on a GPU')
+    x = x.contiguous()
+    n, T = x.shape
+    late, fade = int(late), int(fade)
+    hop = T - 2 * late - fade
+    # (a refused geometry raises below; the buffer only has to exist for the call)
+    out = torch.empty(max((n - 1) * hop + T - 2 * late, 1) if hop > 0 else 1, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().ast_stitch(
+            ctypes.c_void_p(x.data_ptr()), n, T, late, fade, ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)))
+    return out
+
+
 class AdamLoop:
     """The throughput-mode optimiser step on the device: ast_loss_grad + fused Adam over the
     audio buffer ``x`` [B, T] (optimised in place; Adam state and the step counter on the
@@ -303,7 +349,7 @@ class AdamLoop:
 
     def step(self):
         if self.graph is not None:
-            if self._gen != self.eng.gen:   # gamma changed since capture
+            if self._gen != self.eng.gen:   # gamma / anchor changed since capture
                 self._capture()
             self.graph.replay()
         else:
@@ -451,7 +497,7 @@ class LbfgsLoop:
     def step(self):
         if self.use_graph:
             if self.graph is not None and self._gen != self.eng.gen:
-                self.graph = None           # gamma changed since capture: capture again
+                self.graph = None           # gamma / anchor changed since capture: capture again
             if self.graph is None:
                 # captured at the first step after begin(): capture records the pair without
                 # executing it, and the state lives in ws, so every replay is an eager step

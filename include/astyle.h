@@ -20,6 +20,11 @@
  *   ast_set_gamma             <- the --gamma constant of define_loss (methods.py:125)
  *   ast_lbfgs_*               <- scipy L-BFGS-B under ScipyOptimizerInterface.minimize
  *                                (methods.py:132-137,164-181), per clip on the device
+ *   ast_set_anchor /          <- (no reference counterpart) an optional loss term of the long-form
+ *   ast_anchor_loss              mode that pulls a window towards given audio where it overlaps
+ *                                its neighbours
+ *   ast_stitch                <- (no reference counterpart) the join of overlapping optimised
+ *                                windows; the reference writes one window (methods.py:176)
  *   ast_adam_step             <- (new) fused optimiser update on the audio buffer; the
  *                                reference's optimiser is host L-BFGS-B (methods.py:133-137)
  *
@@ -157,6 +162,33 @@ int ast_set_cu_limit(ast_ctx* ctx, int cus);
 
 /* Change gamma (methods.py:125) without rebuilding the context. */
 int ast_set_gamma(ast_ctx* ctx, float gamma);
+
+/* Seam anchor term (no reference counterpart; the long-form mode, longform.py).  Per clip b
+ *   anchor_b = mu * sum_t w[b,t] (a(x[b,t]) - ref[b,t])^2 / sum_t w[b,t]   (0 when sum_t w[b,t] = 0)
+ * with a the TF inv_mu_law of the STFT regulariser (utils.py:92-104).  While set, every
+ * ast_loss_grad adds it to parts[b][0] (the [batch, 4] layout stays: the term's value is the
+ * total minus the other three weighted parts, or ast_anchor_loss) and its gradient
+ * 2 mu w (a - ref) a'(x) / sum w to grad_dev, in phase 2, before the range flags.  Computed in
+ * fp32 whatever the precision, partial sums in a fixed order without atomics: a clip's value and
+ * gradient are bit-identical in any slot of any batch and from run to run.
+ * ref_dev [batch,T] audio units, w_dev [batch,T] >= 0, caller keeps both alive; the values are
+ * read at every evaluation (sum w included), so they may be overwritten in place between
+ * evaluations, also under a captured graph.  ref_dev == NULL or mu == 0 clears the term; unset,
+ * no anchor kernel launches.  Setting or clearing changes the kernels ast_loss_grad launches:
+ * recapture a captured graph. */
+int ast_set_anchor(ast_ctx* ctx, const float* ref_dev, const float* w_dev, float mu);
+/* the term's value (mu included) per clip at the most recent ast_loss_grad; 0 when unset */
+int ast_anchor_loss(ast_ctx* ctx, float* out_dev /*[batch]*/, void* stream);
+
+/* Join n overlapping windows into one signal (no reference counterpart; no context).  Window k
+ * [T] starts hop = T - 2 late - fade samples after window k - 1; the `late` guard samples at both
+ * ends of a window are dropped (methods.py:39,176), neighbours crossfade over `fade` samples with
+ * weights sin^2(pi/2 (j + 1/2) / fade) and one minus that, which sum to 1.  Every output sample
+ * gathers the one or two windows covering it through inv_mu_law_numpy (utils.py:85-90, x == 0 ->
+ * 0); no atomics, deterministic.  AST_E_ARG for T < 4096, fade < 0 or 2 fade > T - 2 late.  Peak
+ * normalisation (methods.py:176) stays with the caller.  Graph-capturable. */
+int ast_stitch(const float* x_dev /*[n,T] mu-law units*/, int n, int T, int late, int fade,
+               float* out_dev /*[(n-1)*hop + T - 2*late] audio*/, void* stream);
 
 /* Fused Adam on the audio buffer: m, v, x updated in place from grad_dev. step >= 1. */
 int ast_adam_step(ast_ctx* ctx, float* x_dev, float* m_dev, float* v_dev, const float* grad_dev,
