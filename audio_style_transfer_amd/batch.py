@@ -91,9 +91,15 @@ def _engine_module(spec):
     return getattr(m, cls), getattr(m, 'LbfgsLoop')
 
 
+def check_args(args):
+    if getattr(args, 'enc', 0.0) != 0:
+        raise ValueError('--enc (the encoding term) is out of scope for the batch mode; use methods')
+
+
 def run_rank(args, pairs, ws, rank, dev, log=print):
     """Optimise this rank's shard of `pairs`; returns {global pair index: final x (float64)}."""
     import torch
+    check_args(args)
     Eng, Loop = _engine_module(args.engine)
     mine = list(clip_range(len(pairs), ws, rank))
     if not mine:
@@ -226,7 +232,12 @@ def run_rank(args, pairs, ws, rank, dev, log=print):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    args = make_parser().parse_args(argv)
+    parser = make_parser()
+    args = parser.parse_args(argv)
+    try:
+        check_args(args)
+    except ValueError as e:
+        parser.error(str(e))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pp = os.environ.get('PYTHONPATH', '')
     rc = launch_ranks(args.gpus, ['-m', 'audio_style_transfer_amd.batch'], argv,

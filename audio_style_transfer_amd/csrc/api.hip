@@ -143,6 +143,15 @@ struct ast_ctx {
     float* anc_part = nullptr;              //   chunk partials [B][anchor_chunks(T)][2]
     float* anc_loss = nullptr;              //   the term's value per clip at the last evaluation [B]
     bool anc_evaluated = false;             //   anc_loss holds an evaluation of the current setting
+    int top_tap = 0;                        // highest tapped tensor (= nblk unless with_encoding forces 30 blocks)
+    const float* enc_phi = nullptr;         // encoding term (ast_set_encoding_target): caller's phi_e
+    int enc_shared = 0;                     //   [B][R][16] ([R][16] when shared); null: term unset
+    float enc_omega = 0.f;
+    float* enc = nullptr;                   //   the encoding at the last evaluation [B][R][16]
+    float* enc_d = nullptr;                 //   enc - phi_e [B][R][16]
+    float* enc_part = nullptr;              //   per-hop squared errors [B][R]
+    float* enc_loss = nullptr;              //   the term's value per clip at the last evaluation [B]
+    bool enc_evaluated = false;             //   enc_loss holds an evaluation of the current setting
     std::vector<const void*> lb_ws;         // workspaces started here with x0 (ast_lbfgs_begin)
     void* zero = nullptr;                   // 256 zero bytes
     int* rflags = nullptr;                  // [B] AST_RANGE_* OR'ed over ast_loss_grad calls since the last reset
@@ -187,6 +196,8 @@ int plan(const ast_cfg* c, ast_ctx* x) {
         return fail(AST_E_ARG, "cnt_channels / nb_channels must be >= 1");
     if (c->precision < 0 || c->precision > 2)
         return fail(AST_E_ARG, "precision must be 0 (fp32), 1 (bf16) or 2 (split: fp32 storage, split-fp16 MFMA)");
+    if (c->with_encoding != 0 && c->with_encoding != 1)
+        return fail(AST_E_ARG, "with_encoding must be 0 or 1");
     int top = 0;
     x->need_bott = false;
     x->ncc = 0;
@@ -218,6 +229,8 @@ int plan(const ast_cfg* c, ast_ctx* x) {
         x->lmap[i] = u;
         x->tensor_in_style[tns] = true;
     }
+    x->top_tap = top;
+    if (c->with_encoding) top = NBLK_MAX;   // the encoding pools e_30 (model.py:121-128): every block runs
     x->nblk = top;
     // every dilation used must divide T (masked.py:134)
     const int maxd = x->nblk >= 10 ? 512 : (1 << (x->nblk - 1));
@@ -337,7 +350,7 @@ size_t workspace_bytes(const ast_cfg* c, const ast_ctx* x) {
     int ncg = 0;
     const int fuse_u = fused_content_occ(x);   // (as ast_create: no content-gradient buffer for it)
     for (int t = 0; t <= NBLK_MAX; ++t)
-        if ((x->tensor_has_direct_content[t] && !(fuse_u >= 0 && x->uid[fuse_u] == t)) || (t == 30 && x->need_bott)) ++ncg;
+        if ((x->tensor_has_direct_content[t] && !(fuse_u >= 0 && x->uid[fuse_u] == t)) || (t == 30 && (x->need_bott || c->with_encoding))) ++ncg;
     n += (size_t)ncg * BTC * es;
     if (x->need_bott) n += 2 * (size_t)c->batch * c->T * 16 * 4;
     n += x->gpart_elems * 4;                                // gpart
@@ -349,6 +362,7 @@ size_t workspace_bytes(const ast_cfg* c, const ast_ctx* x) {
     const int nf = stft_frames(c->T);
     if (nf) n += 1024 * 8 + (size_t)c->batch * nf * (1 + 1024) * 4;   // STFT regulariser
     n += (size_t)c->batch * (2 * anchor_chunks(c->T) + 1) * 4;        // seam anchor partials, values
+    if (c->with_encoding) n += (size_t)c->batch * ((size_t)(c->T / 512) * 33 + 1) * 4;   // enc, d, hop partials, values
     return n;
 }
 
@@ -543,7 +557,7 @@ void launch_gram_bwd_any(ast_ctx* x, const GramArgs& g, hipStream_t s) {
 int fused_content_occ(const ast_ctx* x) {
     static int en = -1;
     if (en < 0) { const char* e = getenv("ASTYLE_FUSE_CONTENT"); en = e ? (atoi(e) != 0) : 1; }
-    if (!en || x->cfg.precision != 2 || x->occ.size() != 1 || x->need_bott) return -1;
+    if (!en || x->cfg.precision != 2 || x->occ.size() != 1 || x->need_bott || x->cfg.with_encoding) return -1;
     const Occ& o = x->occ[0];
     if (o.ext == 31 || !x->tensor_in_style[o.tensor]) return -1;
     if (o.off % 4 || o.ncol % 4 || x->ncc % 4) return -1;   // (float4 phi reads)
@@ -551,12 +565,21 @@ int fused_content_occ(const ast_ctx* x) {
     return -1;
 }
 
+// tensor t's content-gradient buffer as this evaluation writes it (or null): a with_encoding
+// context allocates cg_buf[30] for the encoding term, which nothing writes while the term is unset
+void* cg_live(const ast_ctx* x, int t) {
+    if (t == 30 && !x->need_bott && !x->tensor_has_direct_content[30] && !x->enc_phi) return nullptr;
+    return x->cg_buf[t];
+}
+// the tensor the backward chain starts at: the highest with a loss gradient
+int bwd_top(const ast_ctx* x) { return x->enc_phi ? NBLK_MAX : x->top_tap; }
+
 GramArgs gram_args(ast_ctx* x) {
     GramArgs g;
     memset(&g, 0, sizeof(g));
     g.act = x->act; g.actw = x->dgrad ? x->dgrad : x->act; g.tstride = x->tstride;
     g.nu = x->nu;
-    for (int u = 0; u < x->nu; ++u) { g.uid[u] = x->uid[u]; g.cg[u] = x->cg_buf[x->uid[u]]; }
+    for (int u = 0; u < x->nu; ++u) { g.uid[u] = x->uid[u]; g.cg[u] = cg_live(x, x->uid[u]); }
     g.gpart = x->gpart; g.smat = x->smat; g.zero16 = x->zero;
     g.B = x->cfg.batch; g.T = x->cfg.T; g.nchunk = x->nchunk;
     g.top_u = -1; g.gmax_top = nullptr;
@@ -585,7 +608,7 @@ GatysArgs gatys_args(ast_ctx* x) {
     memset(&g, 0, sizeof(g));
     g.act = x->act; g.actw = x->dgrad ? x->dgrad : x->act; g.tstride = x->tstride;
     g.nu = x->nu;
-    for (int u = 0; u < x->nu; ++u) { g.uid[u] = x->uid[u]; g.cg[u] = x->cg_buf[x->uid[u]]; }
+    for (int u = 0; u < x->nu; ++u) { g.uid[u] = x->uid[u]; g.cg[u] = cg_live(x, x->uid[u]); }
     g.gpart = x->gpart; g.smat = x->smat; g.smatb = x->smatb;
     g.B = x->cfg.batch; g.T = x->cfg.T; g.nchunk = x->nchunk;
     g.cont_u = -1;
@@ -789,7 +812,7 @@ int ast_create(const ast_cfg* cfg, int hip_device, ast_ctx** out) {
     ALLOC(x->chain[1], BTC * x->esz);
     const int fuse_u = fused_content_occ(x);   // (the Gram backward adds that tap's gradient itself)
     for (int t = 0; t <= NBLK_MAX; ++t)
-        if ((x->tensor_has_direct_content[t] && !(fuse_u >= 0 && x->uid[fuse_u] == t)) || (t == 30 && x->need_bott))
+        if ((x->tensor_has_direct_content[t] && !(fuse_u >= 0 && x->uid[fuse_u] == t)) || (t == 30 && (x->need_bott || c.with_encoding)))
             ALLOC(x->cg_buf[t], BTC * x->esz);
     if (x->need_bott) {
         ALLOC(x->bott, (size_t)c.batch * c.T * 16 * 4);
@@ -817,6 +840,13 @@ int ast_create(const ast_cfg* cfg, int hip_device, ast_ctx** out) {
     }
     ALLOC(x->anc_part, (size_t)c.batch * anchor_chunks(c.T) * 2 * 4);
     ALLOC(x->anc_loss, (size_t)c.batch * 4);
+    if (c.with_encoding) {
+        const size_t BR = (size_t)c.batch * (c.T / 512);
+        ALLOC(x->enc, BR * 16 * 4);
+        ALLOC(x->enc_d, BR * 16 * 4);
+        ALLOC(x->enc_part, BR * 4);
+        ALLOC(x->enc_loss, (size_t)c.batch * 4);
+    }
 #undef ALLOC
     x->doop_tune = doop_env() < 0 && x->dgrad &&
                    (size_t)(x->nblk + 1) * x->tstride * x->esz >= ((size_t)4 << 30);
@@ -1079,6 +1109,44 @@ int ast_anchor_loss(ast_ctx* x, float* out, void* stream) {
     return 0;
 }
 
+int ast_encoding(ast_ctx* x, const float* xd, float* out, void* stream) {
+    if (!x || !xd || !out) return fail(AST_E_ARG, "null argument");
+    if (!x->cfg.with_encoding) return fail(AST_E_STATE, "ast_encoding: the context was created without with_encoding");
+    (void)hipSetDevice(x->dev);
+    hipStream_t s = S(stream);
+    const int rc = run_forward(x, xd, s);
+    if (rc) return rc;
+    const ast_cfg& c = x->cfg;
+    if (x->bf) launch_encpool_fwd((const u16*)tens(x, 30), x->wts + WB_OFF, x->wts + BB_OFF, nullptr, 0, out, nullptr, nullptr, c.batch, c.T, s);
+    else launch_encpool_fwd((const float*)tens(x, 30), x->wts + WB_OFF, x->wts + BB_OFF, nullptr, 0, out, nullptr, nullptr, c.batch, c.T, s);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int ast_set_encoding_target(ast_ctx* x, const float* phi_e, int shared, float omega) {
+    if (!x) return fail(AST_E_ARG, "null argument");
+    if (!x->cfg.with_encoding) return fail(AST_E_STATE, "ast_set_encoding_target: the context was created without with_encoding");
+    if (!(omega >= 0.f) || !std::isfinite(omega)) return fail(AST_E_ARG, "ast_set_encoding_target: omega must be finite and >= 0");
+    const bool on = phi_e && omega != 0.f;
+    x->enc_phi = on ? phi_e : nullptr;
+    x->enc_shared = on && shared ? 1 : 0;
+    x->enc_omega = on ? omega : 0.f;
+    x->enc_evaluated = false;
+    x->lg_front_done = false;
+    return 0;
+}
+
+int ast_encoding_loss(ast_ctx* x, float* out, void* stream) {
+    if (!x || !out) return fail(AST_E_ARG, "null argument");
+    if (!x->cfg.with_encoding) return fail(AST_E_STATE, "ast_encoding_loss: the context was created without with_encoding");
+    const size_t nb = (size_t)x->cfg.batch * 4;
+    if (x->enc_phi && x->enc_evaluated)
+        HIPCHK(hipMemcpyAsync(out, x->enc_loss, nb, hipMemcpyDeviceToDevice, S(stream)));
+    else
+        HIPCHK(hipMemsetAsync(out, 0, nb, S(stream)));
+    return 0;
+}
+
 int ast_stitch(const float* xd, int n, int T, int late, int fade, float* out, void* stream) {
     if (!xd || !out) return fail(AST_E_ARG, "null argument");
     if (n < 1) return fail(AST_E_ARG, "ast_stitch: need n >= 1 windows");
@@ -1131,7 +1199,21 @@ static int loss_grad_front(ast_ctx* x, const float* xd, hipStream_t s) {
     if (x->need_bott) {
         if (x->bf) launch_bottleneck_bwd(x->gbott, (u16*)x->cg_buf[30], x->wts + WB_OFF, !first_cg[30], c.batch, c.T, s);
         else launch_bottleneck_bwd(x->gbott, (float*)x->cg_buf[30], x->wts + WB_OFF, !first_cg[30], c.batch, c.T, s);
+        first_cg[30] = false;
     }
+    // encoding term (ast_set_encoding_target; model.py:121-128): here, while tensor 30 still holds
+    // E (the Gram backward may overwrite it in place); nothing launches while it is unset
+    if (x->enc_phi) {
+        const size_t pbs = x->enc_shared ? 0 : (size_t)(c.T / 512) * 16;
+        if (x->bf) {
+            launch_encpool_fwd((const u16*)tens(x, 30), x->wts + WB_OFF, x->wts + BB_OFF, x->enc_phi, pbs, x->enc, x->enc_d, x->enc_part, c.batch, c.T, s);
+            launch_encpool_bwd(x->enc_d, x->wts + WB_OFF, (u16*)x->cg_buf[30], x->enc_omega, !first_cg[30], c.batch, c.T, s);
+        } else {
+            launch_encpool_fwd((const float*)tens(x, 30), x->wts + WB_OFF, x->wts + BB_OFF, x->enc_phi, pbs, x->enc, x->enc_d, x->enc_part, c.batch, c.T, s);
+            launch_encpool_bwd(x->enc_d, x->wts + WB_OFF, (float*)x->cg_buf[30], x->enc_omega, !first_cg[30], c.batch, c.T, s);
+        }
+    }
+    const int ntop = bwd_top(x);
     // style (methods.py:62-76, 118-119)
     tmark(x, s);
     bool& top_max_done = x->lg_top_max_done;   // split: the Gram bwd recorded the top tensor's per-clip max
@@ -1146,9 +1228,9 @@ static int loss_grad_front(ast_ctx* x, const float* xd, hipStream_t s) {
         sa.smat = x->smat; sa.smatb = x->smatb; sa.spart = x->spart;
         launch_style_gatys(sa, s);
         tmark(x, s);
-        if (x->split && x->tensor_in_style[x->nblk]) {   // the chain's first max |tot| inside the Gatys bwd
-            for (int u = 0; u < x->nu; ++u) if (x->uid[u] == x->nblk) g.top_u = u;
-            g.gmax_top = x->gmax_g + (size_t)x->nblk * c.batch * GCLIP_W;
+        if (x->split && x->tensor_in_style[ntop]) {   // the chain's first max |tot| inside the Gatys bwd
+            for (int u = 0; u < x->nu; ++u) if (x->uid[u] == ntop) g.top_u = u;
+            g.gmax_top = x->gmax_g + (size_t)ntop * c.batch * GCLIP_W;
             launch_zero32(x->gmax_g, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4, s, 2);
             top_max_done = g.top_u >= 0;
         }
@@ -1172,9 +1254,9 @@ static int loss_grad_front(ast_ctx* x, const float* xd, hipStream_t s) {
         sa.smat = x->smat; sa.spart = x->spart;
         launch_style_ours(sa, s);
         tmark(x, s);
-        if (x->split && x->tensor_in_style[x->nblk]) {   // the chain's first max |tot| inside the Gram bwd
-            for (int u = 0; u < x->nu; ++u) if (x->uid[u] == x->nblk) g.top_u = u;
-            g.gmax_top = x->gmax_g + (size_t)x->nblk * c.batch * GCLIP_W;
+        if (x->split && x->tensor_in_style[ntop]) {   // the chain's first max |tot| inside the Gram bwd
+            for (int u = 0; u < x->nu; ++u) if (x->uid[u] == ntop) g.top_u = u;
+            g.gmax_top = x->gmax_g + (size_t)ntop * c.batch * GCLIP_W;
             launch_zero32(x->gmax_g, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4, s, 2);
             top_max_done = g.top_u >= 0;
         }
@@ -1200,20 +1282,21 @@ static int loss_grad_back(ast_ctx* x, const float* xd, float* grad, float* parts
     const ast_cfg& c = x->cfg;
     const bool top_max_done = x->lg_top_max_done;
     x->lg_front_done = false;
-    // backward chain through the blocks
+    // backward chain through the blocks, from the highest tensor with a loss gradient
+    const int ntop = bwd_top(x);
     auto direct = [&](int t) -> const void* {   // D_t: direct loss gradient of tensor t (or null)
-        return x->tensor_in_style[t] ? (x->dgrad ? (const void*)((char*)x->dgrad + (size_t)t * x->tstride * x->esz) : tens(x, t)) : x->cg_buf[t];
+        return x->tensor_in_style[t] ? (x->dgrad ? (const void*)((char*)x->dgrad + (size_t)t * x->tstride * x->esz) : tens(x, t)) : cg_live(x, t);
     };
     if (x->split && !top_max_done) {
         launch_zero32(x->gmax_g, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4, s, 2);
-        const void* top = direct(x->nblk);
+        const void* top = direct(ntop);
         if (!top) return fail(AST_E_STATE, "top block has no loss gradient");
-        launch_absmax((const float*)top, (size_t)c.T * C, c.batch, x->gmax_g + (size_t)x->nblk * c.batch * GCLIP_W, s);
+        launch_absmax((const float*)top, (size_t)c.T * C, c.batch, x->gmax_g + (size_t)ntop * c.batch * GCLIP_W, s);
     }
-    for (int l = x->nblk - 1; l >= 0; --l) {
+    for (int l = ntop - 1; l >= 0; --l) {
         float* w = blkw(x, l);
         const int tin = l + 1;
-        const void* gin = (l == x->nblk - 1) ? nullptr : x->chain[(l + 1) & 1];
+        const void* gin = (l == ntop - 1) ? nullptr : x->chain[(l + 1) & 1];
         const void* din = direct(tin);
         const uint32_t* mu = x->mu + (size_t)l * c.batch * c.T * 4;
         const uint32_t* me = x->me + (size_t)l * c.batch * c.T * 4;
@@ -1278,6 +1361,11 @@ static int loss_grad_back(ast_ctx* x, const float* xd, float* grad, float* parts
     // always holds it; its gradient enters grad only through gamma
     launch_stft_reg(xd, x->stft_tw, x->stft_fpart, x->stft_gfr, grad, parts, c.gamma, c.batch,
                     c.T, s);
+    // encoding term (ast_set_encoding_target): its value; the gradient went in through cg_buf[30]
+    if (x->enc_phi) {
+        launch_encpool_loss(x->enc_part, x->enc_loss, parts, x->enc_omega, c.batch, c.T, s);
+        x->enc_evaluated = true;
+    }
     // seam anchor term (ast_set_anchor): nothing launches while it is unset
     if (x->anc_ref) {
         launch_anchor(xd, x->anc_ref, x->anc_w, x->anc_part, grad, parts, x->anc_loss, x->anc_mu,

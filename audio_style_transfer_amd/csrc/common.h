@@ -407,6 +407,21 @@ int anchor_chunks(int T);
 void launch_anchor(const float* x, const float* ref, const float* w, float* part, float* grad,
                    float* parts, float* aloss, float mu, int B, int T, hipStream_t s);
 
+// NSynth encoding (encpool.hip; model.py:121-128, fastgen.py:86-113): enc [B][T/512][16] = the hop
+// means of the bottleneck of e_30; with phi (elements between clips phi_bstride, 0 = shared) also
+// d = enc - phi and the per-hop squared errors epart [B][T/512]
+template <typename S>
+void launch_encpool_fwd(const S* e30, const float* wb, const float* bb, const float* phi,
+                        size_t phi_bstride, float* enc, float* dbuf, float* epart, int B, int T,
+                        hipStream_t s);
+// cg30 [B][T][C] (+)= 2 omega / (16 R 512) W_b d[b, t / 512], as launch_bottleneck_bwd
+template <typename S>
+void launch_encpool_bwd(const float* dbuf, const float* wb, S* cg30, float omega, int accumulate,
+                        int B, int T, hipStream_t s);
+// eloss[b] = omega / (16 R) sum_r epart[b][r], added to parts[b][0]
+void launch_encpool_loss(const float* epart, float* eloss, float* parts, float omega, int B, int T,
+                         hipStream_t s);
+
 // join of overlapping windows (stitch.hip, no reference counterpart)
 void launch_stitch(const float* x, float* out, int n, int T, int late, int fade, hipStream_t s);
 

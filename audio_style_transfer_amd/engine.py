@@ -29,11 +29,26 @@ def resolve_style_ids(stack=None, style_lyr_ids=None):
     return list(range(30))
 
 
+def check_encoding_target(shape, omega, batch, T, with_encoding=True):
+    """The host-side argument rules of StyleEngine.set_encoding_target (no device needed):
+    ``shape`` is phi_e's shape or None."""
+    if not with_encoding:
+        raise _lib.AstError('the engine was built without encoding=True (ast_cfg.with_encoding)')
+    if not np.isfinite(omega) or omega < 0:
+        raise ValueError('omega must be finite and >= 0, got %r' % (omega,))
+    if shape is None:
+        return
+    R = T // 512
+    if tuple(shape) not in ((batch, R, 16), (R, 16)):
+        raise ValueError('phi_e must be [%d, %d, 16] or [%d, 16], got %s' % (batch, R, R, tuple(shape)))
+
+
 class StyleEngine:
     def __init__(self, batch: int, T: int, cont_ids: Sequence[int], style_ids: Sequence[int],
                  cnt_channels: int = 128, nb_channels: int = 128, gatys: bool = False,
                  lambd: float = 100.0, gamma: float = 0.0, precision: str = 'fp32',
-                 device: Optional[torch.device] = None, weights=None, weight_seed: int = 0):
+                 device: Optional[torch.device] = None, weights=None, weight_seed: int = 0,
+                 encoding: bool = False):
         self.lib = _lib.load()
         if device is None:
             device = torch.device('cuda', torch.cuda.current_device())
@@ -48,8 +63,10 @@ class StyleEngine:
         self.cnt_channels = int(cnt_channels)
         self.lambd = float(lambd)
         self.gamma = float(gamma)
-        self.gen = 0    # bumped by every setting a captured graph bakes in (set_gamma, set_anchor)
+        self.gen = 0    # bumped by every setting a captured graph bakes in (set_gamma, set_anchor, set_encoding_target)
         self._anchor = None
+        self.with_encoding = bool(encoding)
+        self._enc_target = None
         cfg = _lib.AstCfg()
         cfg.batch, cfg.T = self.batch, self.T
         cfg.n_cont = len(self.cont_ids)
@@ -64,6 +81,7 @@ class StyleEngine:
         cfg.precision = PRECISIONS[precision]
         cfg.lambd = self.lambd
         cfg.gamma = self.gamma
+        cfg.with_encoding = int(self.with_encoding)
         self.precision = precision
         self._cfg = cfg
         h = ctypes.c_void_p()
@@ -204,6 +222,40 @@ class StyleEngine:
         while the term is unset."""
         out = torch.empty(self.batch, device=self.device)
         _lib.check(self.lib.ast_anchor_loss(self.h, self._ptr(out), self._stream()))
+        return out
+
+    def encoding(self, x: torch.Tensor) -> torch.Tensor:
+        """The NSynth encoding of x [B, T] (model.py:121-128, fastgen.py:86-113): the bottleneck
+        averaged over 512-sample hops, [B, T / 512, 16] float32 (ast_encoding).  Needs
+        ``encoding=True`` at construction."""
+        out = torch.empty(self.batch, self.T // 512, 16, device=self.device)
+        _lib.check(self.lib.ast_encoding(self.h, self._ptr(self._x(x)), self._ptr(out),
+                                         self._stream()))
+        return out
+
+    def set_encoding_target(self, phi_e: Optional[torch.Tensor], omega: float = 0.0) -> None:
+        """The encoding term (ast_set_encoding_target): omega * mean((encoding(x) - phi_e)^2) per
+        clip, added to parts[:, 0] and the gradient of every loss_grad.  phi_e: float32 [B, R, 16]
+        or [R, 16] (shared by every clip), R = T / 512, on the engine's device, used as it is and
+        kept alive here: its values may be overwritten in place between evaluations.
+        ``phi_e=None`` (or omega == 0) clears the term."""
+        omega = float(omega)
+        check_encoding_target(None if phi_e is None else tuple(phi_e.shape), omega, self.batch,
+                              self.T, self.with_encoding)
+        if phi_e is None or omega == 0.0:
+            _lib.check(self.lib.ast_set_encoding_target(self.h, None, 0, 0.0))
+            self._enc_target = None
+        else:
+            _lib.check(self.lib.ast_set_encoding_target(self.h, self._ptr(phi_e),
+                                                        int(phi_e.dim() == 2), omega))
+            self._enc_target = phi_e         # keep alive: the context holds a raw pointer
+        self.gen += 1   # the term's kernels launch only while it is set: recapture
+
+    def encoding_loss(self) -> torch.Tensor:
+        """The encoding term's value per clip [B] (omega included) at the most recent loss_grad;
+        0 while the term is unset."""
+        out = torch.empty(self.batch, device=self.device)
+        _lib.check(self.lib.ast_encoding_loss(self.h, self._ptr(out), self._stream()))
         return out
 
     def loss_grad(self, x: torch.Tensor, grad: Optional[torch.Tensor] = None,

@@ -187,6 +187,8 @@ def check_args(args):
         raise ValueError('--seam must be finite and >= 0')
     if args.chunk < 1:
         raise ValueError('--chunk must be >= 1')
+    if getattr(args, 'enc', 0.0) != 0:
+        raise ValueError('--enc (the encoding term) is out of scope for long-form runs; use methods')
 
 
 def run(args, log=print):

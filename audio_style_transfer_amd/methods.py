@@ -8,7 +8,10 @@ evaluations (methods.py:180), the four loss scalars of every evaluation written 
 file in the log dir (methods.py:127-130,156; summary.EventWriter).  Additions: --optimizer
 device (the same L-BFGS-B on the GPU), --precision split (default) | fp32 | bf16, --weights (npz of TF-named
 encoder variables), --resume (continue after the last finished epoch: each epoch's end point
-is saved as <savepath>/state.npz; an epoch is a fresh minimize call, so x is the whole state).
+is saved as <savepath>/state.npz; an epoch is a fresh minimize call, so x is the whole state),
+--enc OMEGA (an extra loss term omega * mean((encoding(x) - encoding(content clip))^2) on the
+NSynth encoding, model.py:121-128; default 0 = off, a default run is unchanged; whether it
+improves what a listener hears is unmeasured).
 
 --ckpt_path is a TF checkpoint-V2 prefix (model.ckpt-200000: .index + .data shards), read by
 libastyle's native reader without TensorFlow, or an .npz of TF-named arrays; when neither
@@ -59,7 +62,10 @@ class GatysNet(object):
                  logdir='./log', figdir='./data/fig', stack=0, batch_size=16384, sr=16000,
                  cont_lyr_ids=[29], nb_channels=128, cnt_channels=128, gatys=False,
                  style_lyr_ids=None, precision='split', device=None, weights=None, plots=True,
-                 optimizer='scipy', engine_cls=StyleEngine):
+                 optimizer='scipy', engine_cls=StyleEngine, enc=0.0):
+        self.enc = float(enc)       # --enc: weight of the encoding term (0: contexts without it)
+        if not np.isfinite(self.enc) or self.enc < 0:
+            raise ValueError('--enc must be finite and >= 0')
         self.logdir = logdir
         self.savepath = savepath
         self.checkpoint_path = checkpoint_path
@@ -87,10 +93,25 @@ class GatysNet(object):
 
     def build(self, length, batch=1, lambd=100.0, precision=None):
         """methods.py:44-77: encoder + taps + Gram + l2norm, here one libastyle context."""
+        kw = {'encoding': True} if self.enc > 0 else {}
         return self.engine_cls(batch, length, self.cont_lyr_ids, self.style_lyr_ids,
                                cnt_channels=self.cnt_channels, nb_channels=self.nb_channels,
                                gatys=self.gatys, lambd=lambd, precision=precision or self.precision,
-                               device=self.device, weights=self.weights)
+                               device=self.device, weights=self.weights, **kw)
+
+    def get_encoding(self, aud):
+        """The NSynth encoding [T / 512, 16] of one clip (model.py:121-128), mu-law encoded as
+        get_embeds does; needs --enc > 0 (a context built with the encoding)."""
+        aud = np.asarray(aud)[:self.batch_size].reshape(1, self.batch_size)
+        x = torch.tensor(utils.mu_law_numpy(aud), dtype=torch.float32, device=self.device)
+        return self.engine.encoding(x)[0].cpu().numpy()
+
+    def _set_enc(self, eng, phi_e):
+        if self.enc > 0:
+            if phi_e is None:
+                raise ValueError('--enc > 0 needs phi_e (the content clip\'s encoding)')
+            eng.set_encoding_target(torch.as_tensor(phi_e, dtype=torch.float32,
+                                                    device=self.device).contiguous(), self.enc)
 
     def get_embeds(self, *args, is_content=True):
         """methods.py:86-95: mu-law encode the clip and fetch embeds_c or embeds_s.  Accepts the
@@ -123,7 +144,7 @@ class GatysNet(object):
         return phi
 
     def l_bfgs(self, *args, x0=None, log=print, optimizer='scipy', maxiter=100, resume=False,
-               **kw):
+               phi_e=None, **kw):
         """methods.py:140-181 with scipy L-BFGS-B driving ast_loss_grad (``optimizer='scipy'``,
         one host round trip per evaluation, as the reference), or the same L-BFGS-B run on the
         device (``'device'``: ast_lbfgs_*, no round trip; each epoch's evaluations are logged
@@ -146,6 +167,8 @@ class GatysNet(object):
         eng.set_targets(torch.as_tensor(phi_c, dtype=torch.float32),
                         torch.as_tensor(phi_s, dtype=torch.float32))
         eng.set_gamma(gamma)                                              # methods.py:121-125
+        self._phi_e = phi_e
+        self._set_enc(eng, phi_e)     # --enc: on for the whole run, in both optimizers
         T = self.batch_size
         x = np.zeros(T) + 1e-6 if x0 is None else np.asarray(x0, dtype=np.float64)  # methods.py:49-54
         x = x.astype(np.float32).astype(np.float64)       # the TF variable is float32
@@ -155,6 +178,8 @@ class GatysNet(object):
         start_ep = 0
         ckpt = os.path.join(self.savepath, 'state.npz')
         fp = self._run_fingerprint(phi_c, phi_s, lambd, gamma, optimizer)
+        if self.enc > 0:     # the encoding term is part of the run (a default run's fingerprint stays)
+            fp = self._run_fingerprint(phi_e, phi_e, self.enc, gamma, fp)
         if resume and os.path.isfile(ckpt):
             with np.load(ckpt, allow_pickle=False) as z:
                 saved = str(z['fingerprint']) if 'fingerprint' in z.files else None
@@ -268,6 +293,7 @@ class GatysNet(object):
         new.set_targets(torch.as_tensor(phi_c, dtype=torch.float32),
                         torch.as_tensor(phi_s, dtype=torch.float32))
         new.set_gamma(gamma)
+        self._set_enc(new, getattr(self, '_phi_e', None))
         return new
 
     def _run_fingerprint(self, phi_c, phi_s, lambd, gamma, optimizer):
@@ -300,6 +326,8 @@ class GatysNet(object):
         phi = self.get_embeds(aud, is_content=False)
         phi = phi + phi_t - phi_s
         phi = phi / np.sqrt(np.maximum(np.sum(phi * phi, axis=(1, 2), keepdims=True), 1e-12))
+        # --enc: phi_e is the encoding of the same content clip
+        self.phi_e = self.get_encoding(aud) if self.enc > 0 else None
         return phi_c, phi
 
     def run(self, cont_file, source, target, epochs, lambd=0.1, gamma=0.1, audio_channel=0,
@@ -307,7 +335,7 @@ class GatysNet(object):
         """methods.py:183-216."""
         phi_c, phi = self.targets(cont_file, source, target, audio_channel, start)
         x = self.l_bfgs(phi_c, phi, epochs=epochs, lambd=lambd, gamma=gamma,
-                        optimizer=self.optimizer, resume=resume)
+                        optimizer=self.optimizer, resume=resume, phi_e=self.phi_e)
         return utils.inv_mu_law_numpy(x[None])[0]
 
 
@@ -321,7 +349,7 @@ def get_fpath(fn, args):
     return os.path.join(args.dir, fn) + '.wav'
 
 
-EXTRA_FLAGS = ('precision', 'weights', 'no_plots', 'optimizer', 'resume')
+EXTRA_FLAGS = ('precision', 'weights', 'no_plots', 'optimizer', 'resume', 'enc')
 
 
 def piece_work(args):
@@ -334,7 +362,7 @@ def piece_work(args):
     test = GatysNet(savepath, args.ckpt_path, logdir, figdir, args.stack, args.batch_size, args.sr,
                     args.cont_lyrs, args.channels, args.cnt_channels, args.gatys, args.style_lyrs,
                     precision=args.precision, weights=weights, plots=not args.no_plots,
-                    optimizer=args.optimizer)
+                    optimizer=args.optimizer, enc=args.enc)
     return test.run(content, content, style, epochs=args.epochs, lambd=args.lambd,
                     gamma=args.gamma, start=args.start, resume=args.resume)
 
@@ -378,6 +406,10 @@ def make_parser(positionals=True, **kw):
                              'L-BFGS-B on the GPU (ast_lbfgs_*)')
     parser.add_argument('--resume', action='store_true',
                         help='continue after the last finished epoch saved in the output dir')
+    parser.add_argument('--enc', type=float, default=0.0, metavar='OMEGA',
+                        help='weight of the encoding term omega * mean((encoding(x) - encoding('
+                             'content clip))^2) on the NSynth encoding (default 0 = off, the run '
+                             'is unchanged; its effect on audio quality is unmeasured)')
     return parser
 
 

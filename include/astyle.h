@@ -23,6 +23,9 @@
  *   ast_set_anchor /          <- (no reference counterpart) an optional loss term of the long-form
  *   ast_anchor_loss              mode that pulls a window towards given audio where it overlaps
  *                                its neighbours
+ *   ast_encoding /            <- the NSynth encoding: the bottleneck pooled over 512-sample hops
+ *   ast_set_encoding_target /    (model.py:121-128 ae_pool; fastgen.py:86-113 encode), and an
+ *   ast_encoding_loss            optional loss term on it (the term has no reference counterpart)
  *   ast_stitch                <- (no reference counterpart) the join of overlapping optimised
  *                                windows; the reference writes one window (methods.py:176)
  *   ast_adam_step             <- (new) fused optimiser update on the audio buffer; the
@@ -71,6 +74,10 @@ typedef struct ast_cfg {
                                         accumulation), Gram on bf16 MFMA */
     float lambd;                     /* --lambd                      (methods.py:125) */
     float gamma;                     /* --gamma, STFT regulariser    (methods.py:121-125) */
+    int with_encoding;               /* 1: the context can form the NSynth encoding (model.py:121-128,
+                                        fastgen.py:86-113) and carry the encoding term: all 30 blocks
+                                        run, one more content-gradient buffer, the content tap is
+                                        never fused into the Gram backward.  0: as without the field */
 } ast_cfg;
 
 /* Context lifetime. */
@@ -179,6 +186,35 @@ int ast_set_gamma(ast_ctx* ctx, float gamma);
 int ast_set_anchor(ast_ctx* ctx, const float* ref_dev, const float* w_dev, float mu);
 /* the term's value (mu included) per clip at the most recent ast_loss_grad; 0 when unset */
 int ast_anchor_loss(ast_ctx* ctx, float* out_dev /*[batch]*/, void* stream);
+
+/* The NSynth encoding (model.py:121-128 `ae_pool`; fastgen.py:86-113 `encode`): the encoder
+ * forward over x_dev [batch, T], then per clip and 512-sample hop r (R = T / 512)
+ *   enc[b, r, j] = (1/512) sum_{t in hop r} (sum_c e_30[b, t, c] W_b[c, j] + b_b[j]),  j < 16
+ * (ae_bottleneck 1x1, then pool1d window = stride = 512: no padding, a plain mean) to out_dev
+ * [batch, T/512, 16].  The kernel averages the 128 channels over the hop first (rows in a fixed
+ * order), then applies the 1x1 in channel order and adds the bias: the same linear map, and that
+ * order defines the result.  fp32 whatever the precision; a clip's encoding is bit-identical in
+ * any slot of any batch and from run to run.  AST_E_STATE on a context created without
+ * with_encoding.  Graph-capturable. */
+int ast_encoding(ast_ctx* ctx, const float* x_dev, float* out_dev /*[batch, T/512, 16]*/, void* stream);
+/* Encoding term on the encoding above (model.py:121-128, fastgen.py:86-113; the term itself has no
+ * reference counterpart).  Per clip b
+ *   enc_term_b = omega * mean_{r, j} (enc(x)[b, r, j] - phi_e[b, r, j])^2     over all R x 16 entries.
+ * While set, every ast_loss_grad adds it to parts[b][0] (the [batch, 4] layout stays: the term's
+ * value is ast_encoding_loss) in phase 2 after the STFT regulariser and before the anchor term, and
+ * its gradient 2 omega / (16 R 512) sum_j W_b[c, j] (enc - phi_e)[b, t / 512, j] to d loss / d e_30
+ * in phase 1, next to the content taps.  fp32 whatever the precision, sums in a fixed order without
+ * atomics: bit-identical per clip in any slot of any batch, from run to run and under graph replay.
+ * phi_e_dev [batch, R, 16], or [R, 16] when shared != 0; caller keeps it alive; it is read at every
+ * evaluation, so it may be overwritten in place between evaluations, also under a captured graph.
+ * phi_e_dev == NULL or omega == 0 clears the term; unset, no encoding kernel launches and the
+ * backward chain starts at the highest tapped tensor.  omega must be finite and >= 0.  Setting or
+ * clearing changes the kernels ast_loss_grad launches: recapture a captured graph.  AST_E_STATE on
+ * a context created without with_encoding. */
+int ast_set_encoding_target(ast_ctx* ctx, const float* phi_e_dev, int shared, float omega);
+/* the encoding term's value (omega included) per clip at the most recent ast_loss_grad; 0 when
+ * unset (model.py:121-128, fastgen.py:86-113).  AST_E_STATE without with_encoding. */
+int ast_encoding_loss(ast_ctx* ctx, float* out_dev /*[batch]*/, void* stream);
 
 /* Join n overlapping windows into one signal (no reference counterpart; no context).  Window k
  * [T] starts hop = T - 2 late - fade samples after window k - 1; the `late` guard samples at both
