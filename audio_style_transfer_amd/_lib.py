@@ -19,7 +19,9 @@ LBFGS_HISTORY = 4096    # AST_LBFGS_HISTORY: evaluations per minimize call kept 
 # Every symbol include/astyle.h declares (checked by tests/test_abi.py).
 EXPORTS = ('ast_create', 'ast_destroy', 'ast_workspace_bytes', 'ast_d_out_of_place', 'ast_set_weight', 'ast_forward',
            'ast_get_extract', 'ast_embeds', 'ast_content_cols', 'ast_set_targets',
-           'ast_set_gamma', 'ast_set_anchor', 'ast_anchor_loss', 'ast_encoding', 'ast_set_encoding_target', 'ast_encoding_loss', 'ast_stitch', 'ast_loss_grad', 'ast_loss_grad_phase', 'ast_range_flags', 'ast_range_flags_last', 'ast_range_flags_reset', 'ast_set_cu_limit', 'ast_adam_step', 'ast_adam_step_dev',
+           'ast_set_gamma', 'ast_set_anchor', 'ast_anchor_loss', 'ast_encoding', 'ast_set_encoding_target', 'ast_encoding_loss', 'ast_stitch',
+           'ast_dec_workspace_bytes', 'ast_dec_create', 'ast_dec_destroy', 'ast_dec_tables', 'ast_dec_set_weight',
+           'ast_dec_restore', 'ast_dec_reset', 'ast_dec_step', 'ast_dec_position', 'ast_loss_grad', 'ast_loss_grad_phase', 'ast_range_flags', 'ast_range_flags_last', 'ast_range_flags_reset', 'ast_set_cu_limit', 'ast_adam_step', 'ast_adam_step_dev',
            'ast_lbfgs_workspace_bytes', 'ast_lbfgs_begin', 'ast_lbfgs_step', 'ast_lbfgs_state',
            'ast_lbfgs_history',
            'ast_timing', 'ast_timing_read', 'ast_ot_admm', 'ast_ckpt_open', 'ast_ckpt_close',
@@ -35,6 +37,11 @@ class AstCfg(ctypes.Structure):
                 ('nb_channels', ctypes.c_int), ('gatys', ctypes.c_int),
                 ('precision', ctypes.c_int), ('lambd', ctypes.c_float),
                 ('gamma', ctypes.c_float), ('with_encoding', ctypes.c_int)]
+
+
+class AstDecCfg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ('batch', 'width', 'skip_width', 'n_layers', 'n_stages',
+                                            'n_z', 'hop')]
 
 
 class AstError(RuntimeError):
@@ -73,6 +80,15 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         'ast_set_encoding_target': (i, [vp, vp, i, f]),
         'ast_encoding_loss': (i, [vp, vp, vp]),
         'ast_stitch': (i, [vp, i, i, i, i, vp, vp]),
+        'ast_dec_workspace_bytes': (i, [ctypes.POINTER(AstDecCfg), ctypes.POINTER(sz)]),
+        'ast_dec_create': (i, [ctypes.POINTER(AstDecCfg), i, ctypes.POINTER(vp)]),
+        'ast_dec_destroy': (None, [vp]),
+        'ast_dec_tables': (i, [fp, fp]),
+        'ast_dec_set_weight': (i, [vp, ctypes.c_char_p, fp, sz]),
+        'ast_dec_restore': (i, [vp, ctypes.c_char_p]),
+        'ast_dec_reset': (i, [vp, vp]),
+        'ast_dec_step': (i, [vp, vp, i, vp, vp, i, vp, vp, vp, vp]),
+        'ast_dec_position': (i, [vp, vp, vp]),
         'ast_loss_grad': (i, [vp, vp, vp, vp, vp]),
         'ast_loss_grad_phase': (i, [vp, vp, vp, vp, i, vp]),
         'ast_range_flags': (i, [vp, vp, vp]),

@@ -5,6 +5,7 @@ BundleEntryProtos + the .data shards, CRC-checked).  Host only: no GPU is touche
     list_variables(prefix)      -> [(name, shape)]          (tf.train.list_variables)
     read_variables(prefix, names=None) -> {name: float32 ndarray}
     encoder_weights(prefix)     -> the 124 encoder variables StyleEngine.set_weights takes
+    decoder_weights(prefix)     -> the WaveNet decoder's variables synthesis.Decoder takes
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .weights import weight_shapes
+from .weights import decoder_weight_shapes, weight_shapes
 
 
 def is_checkpoint(prefix) -> bool:
@@ -79,5 +80,16 @@ def encoder_weights(prefix):
     for n, s in shapes.items():
         if tuple(w[n].shape) != tuple(s):
             raise _lib.AstError('%s: %s has shape %s, the encoder needs %s'
+                                % (prefix, n, w[n].shape, tuple(s)))
+    return w
+
+
+def decoder_weights(prefix, **sizes):
+    """Every decoder variable (weights.decoder_weight_shapes names), shape-checked."""
+    shapes = decoder_weight_shapes(**sizes)
+    w = read_variables(prefix, list(shapes))
+    for n, s in shapes.items():
+        if tuple(w[n].shape) != tuple(s):
+            raise _lib.AstError('%s: %s has shape %s, the decoder needs %s'
                                 % (prefix, n, w[n].shape, tuple(s)))
     return w

@@ -43,6 +43,39 @@ def synthetic_weights(seed: int = 0, bias_scale: float = 0.05):
     return out
 
 
+def decoder_weight_shapes(width=512, skip_width=256, n_layers=30, n_z=16):
+    """Ordered {tf_name: shape} for the WaveNet decoder (nsynth/wavenet/model.py:28-137)."""
+    def both(shapes, name, shape):
+        shapes[name + '/W'] = shape
+        shapes[name + '/biases'] = (shape[-1],)
+    shapes = {}
+    both(shapes, 'startconv', (1, 3, 1, width))
+    both(shapes, 'skip_start', (1, 1, width, skip_width))
+    for l in range(1, n_layers + 1):
+        both(shapes, 'dilatedconv_%d' % l, (1, 3, width, 2 * width))
+        both(shapes, 'cond_map_%d' % l, (1, 1, n_z, 2 * width))
+        both(shapes, 'res_%d' % l, (1, 1, width, width))
+        both(shapes, 'skip_%d' % l, (1, 1, width, skip_width))
+    both(shapes, 'out1', (1, 1, skip_width, skip_width))
+    both(shapes, 'cond_map_out1', (1, 1, n_z, skip_width))
+    both(shapes, 'logits', (1, 1, skip_width, 256))
+    return shapes
+
+
+def synthetic_decoder_weights(seed: int = 0, bias_scale: float = 0.05, **sizes):
+    """Deterministic (PCG64) decoder weights by the encoder's initialiser rule (synthetic_weights),
+    float32, keyed by TF variable name; ``sizes`` as decoder_weight_shapes."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = {}
+    for name, shape in decoder_weight_shapes(**sizes).items():
+        if name.endswith('/W'):
+            lim = np.sqrt(3.0 / int(np.prod(shape[:-1])))
+            out[name] = rng.uniform(-lim, lim, size=shape).astype(np.float32)
+        else:
+            out[name] = rng.uniform(-bias_scale, bias_scale, size=shape).astype(np.float32)
+    return out
+
+
 def synthetic_clips(n: int, T: int, seed0: int, sr: int = 16000):
     """Seeded test audio: per clip a mixture of 3 sinusoids (80-2000 Hz)
     plus 0.05*N(0,1), peak-normalised to 0.9; float32 in [-1, 1]."""

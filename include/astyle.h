@@ -26,6 +26,10 @@
  *   ast_encoding /            <- the NSynth encoding: the bottleneck pooled over 512-sample hops
  *   ast_set_encoding_target /    (model.py:121-128 ae_pool; fastgen.py:86-113 encode), and an
  *   ast_encoding_loss            optional loss term on it (the term has no reference counterpart)
+ *   ast_dec_*                 <- the NSynth WaveNet decoder, one sample step per call:
+ *                                FastGenerationConfig.build (nsynth/wavenet/model.py:28-137),
+ *                                causal_linear / linear (nsynth/utils.py:838-908) and the loop
+ *                                body of fastgen.synthesize (fastgen.py:160-212)
  *   ast_stitch                <- (no reference counterpart) the join of overlapping optimised
  *                                windows; the reference writes one window (methods.py:176)
  *   ast_adam_step             <- (new) fused optimiser update on the audio buffer; the
@@ -215,6 +219,62 @@ int ast_set_encoding_target(ast_ctx* ctx, const float* phi_e_dev, int shared, fl
 /* the encoding term's value (omega included) per clip at the most recent ast_loss_grad; 0 when
  * unset (model.py:121-128, fastgen.py:86-113).  AST_E_STATE without with_encoding. */
 int ast_encoding_loss(ast_ctx* ctx, float* out_dev /*[batch]*/, void* stream);
+
+/* The NSynth WaveNet decoder (nsynth/wavenet/model.py:28-137 FastGenerationConfig; nsynth/utils.py:
+ * 838-908 causal_linear / linear; fastgen.py:160-212 synthesize), one sample step per call.  A
+ * context of its own: it shares nothing with an ast_ctx.  Per clip b and step t, with x the
+ * previous step's sample (0 at t = 0) and en = enc[b, t / hop]:
+ *   x_s = mu_law(x) / 128;  l = startconv(x_s(t-2), x_s(t-1), x_s(t));  s = skip_start(l)
+ *   layer i, rate r = 2^(i mod n_stages):
+ *     a = W_i[0] l(t-2r) + W_i[1] l(t-r) + W_i[2] l(t) + b_i + cond_map_i(en)     (l(t') = 0 for t' < 0)
+ *     d = sigmoid(a[:width]) tanh(a[width:]);  l += res_i(d);  s += skip_i(d)
+ *   s = relu(s);  s = relu(out1(s) + cond_map_out1(en));  pmf = softmax(logits(s))          256 bins
+ *   cdf = running fp32 sum of pmf in bin order;  bin = min(first k with cdf[k] >= u, 255)
+ *   audio = inv_mu_law_numpy(bin - 128)
+ * The clamp to 255 is the one deviation: np.searchsorted returns 256 when rounding leaves
+ * cdf[255] < u, and the reference then decodes a bin that does not exist.  bin -> audio and
+ * bin -> the next x_s go through two 256-entry fp32 tables filled on the host at create
+ * (ast_dec_tables): inv_mu_law_numpy (nsynth/utils.py:122-136) in float64 cast to float32, then
+ * mu_law (nsynth/utils.py:70-85) with floor, / 128.  All products are fp32 MFMA with fp32
+ * accumulation in a fixed order (csrc/decoder.hip), no atomics: a clip's pmf and bins are
+ * bit-identical at batch 1 and in any slot of any batch, from run to run and under graph replay. */
+typedef struct ast_dec ast_dec;
+typedef struct ast_dec_cfg {
+    int batch;        /* clips, 1..256 */
+    int width;        /* residual channels (the reference: 512), a multiple of 64 */
+    int skip_width;   /* skip channels (256), a multiple of 32, at most 352 */
+    int n_layers;     /* 30; 1..64 */
+    int n_stages;     /* 10: layer i has rate 2^(i mod n_stages); 1..16 */
+    int n_z;          /* encoding channels: 16 */
+    int hop;          /* samples per encoding row (512), >= 1 */
+} ast_dec_cfg;
+/* Device bytes ast_dec_create(cfg) allocates: weights, state and the per-layer rings
+ * [2 rate][batch][width].  AST_E_ARG with a message for a configuration outside the ranges above. */
+int ast_dec_workspace_bytes(const ast_dec_cfg* cfg, size_t* out_bytes);
+/* The configuration is validated before the device is touched.  Nothing allocates after create. */
+int ast_dec_create(const ast_dec_cfg* cfg, int hip_device, ast_dec** out);
+void ast_dec_destroy(ast_dec* dec);
+/* The two tables of the draw (above), host only: audio256[bin], xs256[bin] = the next step's x_s. */
+int ast_dec_tables(float* audio256, float* xs256);
+/* One variable by its TF name: startconv, skip_start, dilatedconv_k, cond_map_k, res_k, skip_k
+ * (k = 1..n_layers), out1, cond_map_out1, logits; each with /W (HWIO float32) and /biases.
+ * AST_E_NAME for an unknown name or a wrong element count. */
+int ast_dec_set_weight(ast_dec* dec, const char* tf_name, const float* host, size_t n);
+/* Saver.restore (fastgen.py:182-183): every decoder variable from a checkpoint-V2 prefix. */
+int ast_dec_restore(ast_dec* dec, const char* prefix);
+/* init_ops (fastgen.py:186): every queue reads as zero, position 0, input sample 0.  Graph-capturable. */
+int ast_dec_reset(ast_dec* dec, void* stream);
+/* One sample step at the position t kept in device memory: reads enc_dev [batch, R, n_z] row
+ * t / hop and u_dev[b, t], writes bins_dev[b, t], audio_dev[b, t] and, when pmf_dev is not NULL,
+ * pmf_dev[b, t, 0..255], then advances t.  At t >= total it does nothing, so a captured graph of
+ * K calls replayed ceil(total / K) times is the whole synthesis.  With force_dev (int
+ * [batch, total], values 0..255) the next step's input comes from force_dev[b, t] instead of the
+ * drawn bin (teacher forcing); the bin is still drawn and written.  total must be in 1..R hop
+ * (AST_E_ARG).  Launches only: graph-capturable with stable pointers. */
+int ast_dec_step(ast_dec* dec, const float* enc_dev, int R, const float* u_dev, const int* force_dev,
+                 int total, int* bins_dev, float* audio_dev, float* pmf_dev, void* stream);
+/* *out_dev = t.  Graph-capturable. */
+int ast_dec_position(ast_dec* dec, int* out_dev, void* stream);
 
 /* Join n overlapping windows into one signal (no reference counterpart; no context).  Window k
  * [T] starts hop = T - 2 late - fade samples after window k - 1; the `late` guard samples at both
