@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libastyle.so')
 SOURCES = ['encoder.hip', 'block_fwd_bf16.hip', 'block_bwd_bf16.hip', 'block_fwd_split.hip',
            'block_bwd_split.hip', 'block_bwd_split16.hip', 'gram.hip', 'gram_bf16.hip', 'gram_split.hip', 'gram_gatys.hip',
-           'stft_reg.hip', 'anchor.hip', 'encpool.hip', 'decoder.hip', 'stitch.hip', 'lbfgs.hip', 'ot_admm.hip', 'api.hip', 'ckpt.cpp']
+           'stft_reg.hip', 'anchor.hip', 'encpool.hip', 'decoder.hip', 'decoder_score.hip', 'stitch.hip', 'lbfgs.hip', 'ot_admm.hip', 'api.hip', 'ckpt.cpp']
 # tools-only A/B builds (ASTYLE_VARIANT=<name> [ASTYLE_DEFS=...] -> libastyle_<name>.so) may add
 # sources from tools/variants here; round 6 retired the round-3/4 alternative forward kernels
 # (role split, double-buffered image, Winograd timing probes: written for the 32x32x16 fragment

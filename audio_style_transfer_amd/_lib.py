@@ -21,7 +21,8 @@ EXPORTS = ('ast_create', 'ast_destroy', 'ast_workspace_bytes', 'ast_d_out_of_pla
            'ast_get_extract', 'ast_embeds', 'ast_content_cols', 'ast_set_targets',
            'ast_set_gamma', 'ast_set_anchor', 'ast_anchor_loss', 'ast_encoding', 'ast_set_encoding_target', 'ast_encoding_loss', 'ast_stitch',
            'ast_dec_workspace_bytes', 'ast_dec_create', 'ast_dec_destroy', 'ast_dec_tables', 'ast_dec_set_weight',
-           'ast_dec_restore', 'ast_dec_reset', 'ast_dec_step', 'ast_dec_position', 'ast_loss_grad', 'ast_loss_grad_phase', 'ast_range_flags', 'ast_range_flags_last', 'ast_range_flags_reset', 'ast_set_cu_limit', 'ast_adam_step', 'ast_adam_step_dev',
+           'ast_dec_restore', 'ast_dec_reset', 'ast_dec_step', 'ast_dec_position',
+           'ast_dec_score_workspace_bytes', 'ast_dec_score', 'ast_loss_grad', 'ast_loss_grad_phase', 'ast_range_flags', 'ast_range_flags_last', 'ast_range_flags_reset', 'ast_set_cu_limit', 'ast_adam_step', 'ast_adam_step_dev',
            'ast_lbfgs_workspace_bytes', 'ast_lbfgs_begin', 'ast_lbfgs_step', 'ast_lbfgs_state',
            'ast_lbfgs_history',
            'ast_timing', 'ast_timing_read', 'ast_ot_admm', 'ast_ckpt_open', 'ast_ckpt_close',
@@ -89,6 +90,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         'ast_dec_reset': (i, [vp, vp]),
         'ast_dec_step': (i, [vp, vp, i, vp, vp, i, vp, vp, vp, vp]),
         'ast_dec_position': (i, [vp, vp, vp]),
+        'ast_dec_score_workspace_bytes': (i, [ctypes.POINTER(AstDecCfg), i, i, ctypes.POINTER(sz)]),
+        'ast_dec_score': (i, [vp, vp, vp, i, i, i, i, vp, sz, vp, vp, vp, vp, vp]),
         'ast_loss_grad': (i, [vp, vp, vp, vp, vp]),
         'ast_loss_grad_phase': (i, [vp, vp, vp, vp, i, vp]),
         'ast_range_flags': (i, [vp, vp, vp]),

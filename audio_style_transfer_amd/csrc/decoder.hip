@@ -32,10 +32,7 @@
 
 #include "../../include/astyle.h"
 #include "ckpt.h"
-
-namespace ast {
-int set_error(int code, const std::string& msg);   // api.hip
-}
+#include "decoder.h"
 
 namespace {
 
@@ -378,20 +375,6 @@ size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
-struct ast_dec {
-    ast_dec_cfg c;
-    int dev = 0, ntile = 0;
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
-    float *A_skip0, *wstart, *bstart, *bskip0;
-    float *A_gate, *bdil, *bcond, *A_mix, *bres, *bskip;
-    float *A1, *b1, *bc1, *A2, *b2, *tab_audio, *tab_xs;
-    float *l, *s, *d, *ring, *xq;
-    int* pos;
-    std::vector<size_t> ring_off;   // floats, per layer
-    size_t gate_sz = 0, mix_sz = 0; // floats per layer
-};
-
 namespace {
 
 int rate_of(const ast_dec_cfg& c, int layer) { return 1 << (layer % c.n_stages); }
@@ -528,6 +511,10 @@ void fill_tables(float* audio, float* xs) {
 }
 
 }  // namespace
+
+namespace ast {
+int dec_check_cfg(const ast_dec_cfg* c) { return check_cfg(c); }
+}
 
 extern "C" {
 

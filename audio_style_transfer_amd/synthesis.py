@@ -53,6 +53,7 @@ class Decoder(object):
             raise _lib.AstError('Decoder needs a GPU device, got %s' % device)
         self.device = device
         self.batch, self.hop, self.graph_steps = int(batch), int(hop), int(graph_steps)
+        self.n_stages = int(n_stages)
         self.sizes = dict(width=width, skip_width=skip_width, n_layers=n_layers, n_z=N_Z)
         cfg = _lib.AstDecCfg(batch, width, skip_width, n_layers, n_stages, N_Z, hop)
         h = ctypes.c_void_p()
@@ -75,6 +76,7 @@ class Decoder(object):
     def close(self):
         if getattr(self, 'h', None):
             self.graph = None
+            self._score_work = None
             self.torch.cuda.synchronize(self.device)
             self.lib.ast_dec_destroy(self.h)
             self.h = None
@@ -165,6 +167,66 @@ class Decoder(object):
     def position(self):
         _lib.check(self.lib.ast_dec_position(self.h, self._p(self._pos), self._stream()))
         return int(self._pos.item())
+
+    # ------------------------------------------------------------------ scoring
+    def score(self, bins, enc, input_mode=0, want_pmf=False, want_logits=False):
+        """The decoder teacher-forced on ``bins`` int [B, T] (0..255) under ``enc`` [B, R, 16],
+        T <= R hop (ast_dec_score): dict of logp [B, T] = log p(bins[t] | bins[<t], enc),
+        nll [B] (nats per sample), bits = nll / ln 2 and optionally pmf / logits [B, T, 256], as
+        numpy arrays.  input_mode 0 feeds the synthesis table back, 1 (bin - 128) / 128 (the
+        training graph).  B is independent of the context's batch; the synthesis state is not
+        touched.  The work area is a cached tensor that grows as needed."""
+        torch = self.torch
+        dev = self.device
+        b = np.asarray(bins)
+        e = np.asarray(enc, dtype=np.float32)
+        if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] < 1 or not np.issubdtype(b.dtype, np.integer):
+            raise _lib.AstError('score: bins must be integers [batch, T], got %s %s' % (b.dtype, b.shape))
+        if e.ndim != 3 or e.shape[0] != b.shape[0] or e.shape[2] != N_Z:
+            raise _lib.AstError('score: enc %s does not fit bins %s' % (e.shape, b.shape))
+        if b.min() < 0 or b.max() >= NBIN:
+            raise _lib.AstError('score: bins must lie in 0..255, got %d..%d' % (b.min(), b.max()))
+        B, T = b.shape
+        R = e.shape[1]
+        if T > R * self.hop:
+            raise _lib.AstError('score: T %d exceeds R hop = %d' % (T, R * self.hop))
+        if input_mode not in (0, 1):
+            raise _lib.AstError('score: input_mode %r, must be 0 or 1' % (input_mode,))
+        st = self._score_buffers(B, T, want_pmf, want_logits)
+        st['bins'].copy_(torch.as_tensor(b.astype(np.int32)))
+        enc_dev = torch.as_tensor(e, device=dev).contiguous()
+        self._score_launch(st, enc_dev, R, input_mode)
+        out = dict(logp=st['logp'].cpu().numpy(), nll=st['nll'].cpu().numpy())
+        out['bits'] = out['nll'] / np.float32(np.log(2.0))
+        for k in ('pmf', 'logits'):
+            if st[k] is not None:
+                out[k] = st[k].cpu().numpy()
+        return out
+
+    def _score_buffers(self, B, T, want_pmf=False, want_logits=False):
+        torch = self.torch
+        dev = self.device
+        n = ctypes.c_size_t()
+        c = self.sizes
+        cfg = _lib.AstDecCfg(self.batch, c['width'], c['skip_width'], c['n_layers'], self.n_stages, N_Z, self.hop)
+        _lib.check(self.lib.ast_dec_score_workspace_bytes(ctypes.byref(cfg), B, T, ctypes.byref(n)))
+        work = getattr(self, '_score_work', None)
+        if work is None or work.numel() < n.value:
+            self._score_work = work = None          # release before growing
+            self._score_work = work = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        return dict(work=work, need=n.value, B=B, T=T,
+                    bins=torch.empty(B, T, dtype=torch.int32, device=dev),
+                    logp=torch.empty(B, T, dtype=torch.float32, device=dev),
+                    nll=torch.empty(B, dtype=torch.float32, device=dev),
+                    pmf=torch.empty(B, T, NBIN, dtype=torch.float32, device=dev) if want_pmf else None,
+                    logits=torch.empty(B, T, NBIN, dtype=torch.float32, device=dev) if want_logits else None)
+
+    def _score_launch(self, st, enc_dev, R, input_mode):
+        """Launches only (graph-capturable): ast_dec_score on the buffers of _score_buffers."""
+        _lib.check(self.lib.ast_dec_score(self.h, self._p(st['bins']), self._p(enc_dev), st['B'], R, st['T'],
+                                          int(input_mode), self._p(st['work']), st['work'].numel(),
+                                          self._p(st['logp']), self._p(st['nll']), self._p(st['pmf']),
+                                          self._p(st['logits']), self._stream()))
 
     def bins(self):
         return self.bins_dev.cpu().numpy()

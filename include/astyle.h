@@ -30,6 +30,9 @@
  *                                FastGenerationConfig.build (nsynth/wavenet/model.py:28-137),
  *                                causal_linear / linear (nsynth/utils.py:838-908) and the loop
  *                                body of fastgen.synthesize (fastgen.py:160-212)
+ *   ast_dec_score             <- the decoder of Config.build teacher-forced on a given waveform
+ *                                and its loss (nsynth/wavenet/model.py:264-320): log-likelihood
+ *                                per sample and the mean negative log-likelihood per clip
  *   ast_stitch                <- (no reference counterpart) the join of overlapping optimised
  *                                windows; the reference writes one window (methods.py:176)
  *   ast_adam_step             <- (new) fused optimiser update on the audio buffer; the
@@ -275,6 +278,34 @@ int ast_dec_step(ast_dec* dec, const float* enc_dev, int R, const float* u_dev, 
                  int total, int* bins_dev, float* audio_dev, float* pmf_dev, void* stream);
 /* *out_dev = t.  Graph-capturable. */
 int ast_dec_position(ast_dec* dec, int* out_dev, void* stream);
+
+/* Scoring: the decoder teacher-forced over whole sequences (Config.build, model.py:264-320), the
+ * same network and weights as the step form above with time on the GEMMs' N side
+ * (csrc/decoder_score.hip).  For clip b and t < T, with x_s(0) = 0 and x_s(t) = table[bins[b, t-1]]
+ * (masked.shift_right), the step form's layers give logits[b, t]; then
+ *   logp[b, t] = log_softmax(logits[b, t])[bins[b, t]] = (logit[label] - max) - logf(sum exp(. - max))
+ *   nll[b]     = -(1/T) sum_t logp[b, t]                  (fp64 sum in a fixed order; nats per sample)
+ * input_mode 0: table = xs256 of ast_dec_tables, the synthesis feedback, so a synthesised clip is
+ * scored under exactly the distributions it was drawn from; input_mode 1: table[bin] =
+ * (bin - 128) / 128, the training graph's input (model.py:213-214, 264), and nll is its `loss`.
+ * fp32 MFMA with fp32 accumulation, one accumulation order per output element whatever batch, slot
+ * or T: a clip's outputs are bit-identical at batch 1 and in any slot, and a run on a prefix equals
+ * the first columns of the run on the whole sequence.  The label is clamped to 0..255 on the device
+ * for memory safety only: callers pass bins in range.
+ *
+ * The work area (l, d [batch, T, width], s [batch, T, skip_width]) is the caller's; the score batch
+ * is independent of cfg.batch.  Host only: its bytes.  AST_E_ARG for an invalid configuration,
+ * batch outside 1..65535 or T < 1. */
+int ast_dec_score_workspace_bytes(const ast_dec_cfg* cfg, int batch, int T, size_t* out_bytes);
+/* bins_dev int [batch, T], enc_dev [batch, R, n_z] (row t / hop conditions sample t).  Writes
+ * logp_dev [batch, T], nll_dev [batch] and, when not NULL, pmf_dev / logits_dev [batch, T, 256].
+ * Reads the context's weights and writes none of its synthesis state (l, s, d, rings, position,
+ * x queue).  AST_E_ARG with a message, before any launch, for batch < 1, T outside 1..R hop,
+ * input_mode not 0 or 1, a NULL required pointer, or work_bytes below
+ * ast_dec_score_workspace_bytes.  Launches only: graph-capturable with stable pointers. */
+int ast_dec_score(ast_dec* dec, const int* bins_dev, const float* enc_dev, int batch, int R, int T,
+                  int input_mode, void* work_dev, size_t work_bytes, float* logp_dev, float* nll_dev,
+                  float* pmf_dev, float* logits_dev, void* stream);
 
 /* Join n overlapping windows into one signal (no reference counterpart; no context).  Window k
  * [T] starts hop = T - 2 late - fade samples after window k - 1; the `late` guard samples at both
