@@ -11,7 +11,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, 'csrc')
 LIB = os.path.join(PKG, 'libastyle.so')
 SOURCES = ['encoder.hip', 'block_fwd_bf16.hip', 'block_bwd_bf16.hip', 'block_fwd_split.hip',
-           'block_bwd_split.hip', 'block_bwd_split16.hip', 'gram.hip', 'gram_bf16.hip', 'gram_split.hip', 'gram_gatys.hip',
+           'block_bwd_split.hip', 'gram.hip', 'gram_bf16.hip', 'gram_split.hip', 'gram_gatys.hip',
            'stft_reg.hip', 'anchor.hip', 'encpool.hip', 'decoder.hip', 'decoder_score.hip', 'stitch.hip', 'lbfgs.hip', 'ot_admm.hip', 'api.hip', 'ckpt.cpp']
 # tools-only A/B builds (ASTYLE_VARIANT=<name> [ASTYLE_DEFS=...] -> libastyle_<name>.so) may add
 # sources from tools/variants here; round 6 retired the round-3/4 alternative forward kernels
@@ -32,7 +32,7 @@ _CW = ['-mllvm', '-amdgpu-mfma-vgpr-form=1', '-mllvm', '-amdgpu-atomic-optimizer
 if os.environ.get('ASTYLE_NO_VGPR_FORM'):   # A/B builds: let the compiler place MFMA accumulators (AGPRs)
     _CW = _CW[2:]
 EXTRA = {'block_fwd_bf16.hip': _CW, 'block_bwd_bf16.hip': _CW, 'block_fwd_split.hip': _CW,
-         'block_bwd_split.hip': _CW, 'block_bwd_split16.hip': _CW}
+         'block_bwd_split.hip': _CW}
 
 
 def _stale(lib: str = LIB, extra=()) -> bool:

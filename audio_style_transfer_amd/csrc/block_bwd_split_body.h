@@ -1,64 +1,7 @@
-// ASTYLE_MFMA16=1 (round 6): the backward block kernel of block_bwd_split.hip on
-// v_mfma_f32_16x16x32_f16 fragments (splitwave.h "16x16x32"; the weights are packed for it when the
-// knob is set).  Same structure, phases and numerics class; the K accumulation order differs, so
-// results match the default kernels to fp32 rounding, not bit for bit.  Measured (DESIGN.md §3,
-// round 6): as fast as the 32x32x16 default (within 0.3 %) at equal data; kept as the
-// measured alternative, not the default.
+// The backward block kernel's body (block_bwd_split.hip, which includes this file once per MFMA
+// form): the kernel SW_KERNEL on fragments of shape SW_FRAG (splitwave.h Frag32 / Frag16).  The
+// body stays inside the __global__ function: called from a wrapper it compiles to other code.
 //
-// Split-fp16 encoder block backward (precision 2): d loss / d e_l for one block of
-// model.py:95-116, restated by oracle/astyle_oracle.py:171-189 (encoder_backward):
-//   tot = d loss / d e_{l+1} (the chain, its own direct loss term included)
-//   g_u = [u > 0] (W_r tot)                         1x1 conv transposed
-//   g_a = sum_k W_d[k] g_u(p - k + 1)                K = 3 SAME dilated conv transposed, in
-//                                                    time_to_batch positions (masked.py:110-160)
-//   out = tot + D_l + [e_l > 0] g_a                  D_l: direct loss gradient of e_l, if tapped
-// fp32 storage, split fp16 operands on v_mfma_f32_16x16x32_f16 (round 6; 32x32x16 before), fp32
-// accumulation and epilogue (splitwave.h).
-//
-// One workgroup per CU (wave w owns channels 32 w .. 32 w + 31), persistent over tiles of 64
-// positions, one wave per SIMD; the structure of the forward (block_fwd_split.hip): a tile's
-// tot and D_l rows arrive in registers a tile ahead in row units (8 cache lines per wave
-// instruction) and are converted during the previous tile's second GEMM into the split tot
-// image and the wave's quarter of a residual buffer (tot + D_l in fp32, double-buffered, read
-// back by the same wave); the relu-mask words come by plain loads.  Per tile i:
-//   T  barrier (tot image i complete)
-//   A  g_v = W_r tot, column half 0 (8 k-steps x 3 products); carries epilogue half 1 of tile
-//      i-1 (out = residual + [e_l > 0] g_a 2^-(m_u+k_d) -> HBM)
-//   B  g_v column half 1; carries the rest of that epilogue and g_u of half 0 (mask, scale
-//      2^m_u from the bound |g_v| <= wrn max|tot|, split -> g_u image)
-//   H  (one-segment layouts, unless the workgroup's previous tile is the left neighbour: then
-//      its g_u rows 64 / 65 are copied to rows 0 / 1) g_v of rows 0 / 1 (positions p0 - 1, p0;
-//      the column tiles cover p0 + 1 .. p0 + 64); carries g_u of half 1; g_u of the last column
-//      tile; barrier (g_u image complete, tot image free).  The left neighbour includes the
-//      last tile of the previous sub-sequence (CARRY): that tile's right-halo column (p0 + 64,
-//      SAME padding for its own g_a) is computed on the next sub-sequence's first position
-//      instead of a zero row and set aside in g_u row 67, so the next tile's rows 0 / 1 are
-//      (0, row 67) and no tile of a walk pays the halo MFMAs but its first
-//   C  g_a, column half 0 (3 taps x 8 k-steps x 3 products over the g_u image); carries the
-//      conversion of tile i+1 and, unit by unit behind it, the row loads of tile i+2
-//   D  g_a, column half 1; carries epilogue half 0 of tile i
-// The first tile is peeled so every loop iteration issues the same vector-memory sequence.
-// non-temporal (nt) row loads; the stores keep the default policy: they leave the accumulator
-// layout as 16-B pieces of 32 lines per instruction, which L2 merges into whole lines, and nt made
-// them partial-line writes to DRAM (+75 % per launch, profiles/r6_diag/block_ab.txt)
-#ifndef SW_BWD_DEFAULT_POLICY
-#define SW_LD_AUX 2
-#endif
-#include "splitwave.h"
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <type_traits>
-
-namespace ast {
-namespace {
-using namespace sw;
-
-constexpr int IROWS = 72;             // tot image / residual rows (9 units x 8)
-constexpr int ISLOT = IROWS * RS;
-constexpr int GROWS = 68;             // g_u image rows (66 / 68 used; 66 takes unused halo writes)
-constexpr int LA = 2;                 // B-fragment lookahead (steps)
-
 // SX (block 0, one-segment layout, d = 1, no D_0): the start conv's backward folded into the
 // epilogue -- out = d loss / d e_0 is not stored; per position the wave's three dot products
 // sum_c W0[k][c] out[t][c] over its 32 channels go to spart (launch_startx_gx sums the four
@@ -67,7 +10,8 @@ constexpr int LA = 2;                 // B-fragment lookahead (steps)
 // halo rows (p0 - 1, p0 + 64) are SAME padding, so the column tiles cover p0 .. p0 + 63 and rows
 // 0 / 65 of the g_u image stay zero: no halo MFMA tile
 template <bool MASKED, bool ONESEG, bool HAS_D, bool SX, bool WHOLE>
-__global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
+__global__ void __launch_bounds__(FT, 1) SW_KERNEL(BwdArgsS a, Layout) {
+    using S = SW_FRAG;
     // the layout as compile-time constants (pick_layout: one segment or masked: M = 64 with two
     // halo rows; else segments of SEGM = 32 with their pad rows), not the launch argument
     constexpr bool GEO1 = ONESEG || MASKED;
@@ -83,7 +27,7 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
     const int ntiles = a.B * tiles;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int i16 = lane & 15, q4 = lane >> 4;   // 16x16x32 fragment lane (splitwave.h)
+    const S fs(lane, w);                         // the lane's fragment coordinates (splitwave.h)
     const int G = (int)gridDim.x;
     STAMP_DECL
 
@@ -118,24 +62,29 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
     if (SX)   // (read after the first tile's T barrier)
         for (int i = tid; i < 3 * C; i += FT) W0S[i] = a.w0[i];
 
-    // image row and time offset of the lane's column 16 cb + i16 of column half j
-    int Lc[2][2], toff[2][2];
+    // image row and time offset of the lane's column of column half j, column block cb
+    int Lc[2][S::NCB], toff[2][S::NCB];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            Lc[j][cb] = frow(32 * j + 16 * cb + i16, ly);
+        for (int cb = 0; cb < S::NCB; ++cb) {
+            Lc[j][cb] = frow(fs.col(j, cb), ly);
             toff[j][cb] = MASKED ? 0 : row_toff(Lc[j][cb], ly, a.d);
         }
-    const int chq = 32 * w + 4 * q4;  // first channel of this lane's sub-tiles (+ 16 rb)
-    const int mg0 = q4 >> 1;          // mask group of row block 0 (mgrp: + 2 rb); word h = q4 & 1
-    const int mwo = 4 * (q4 & 1) + w; // the lane's word of a position's 8 mask words
+    // unit g of a column half = (column block S::cb(g), row block rb = g % UR): channels
+    // ch0 + CHR rb .. + 3, mask group mg0 + MGR rb.  The lambdas form rb once per unit and the
+    // rest from it: with S::choff(g) / S::mgoff(g) at each use the 16x16x32 kernels compile to
+    // other code
+    constexpr int UR = 4 / S::NCB, CHR = 32 / UR, MGR = S::NCB;
+    const int ch0 = fs.ch0();     // first channel of this lane's unit 0
+    const int mg0 = fs.mg0();     // mask group of unit 0
+    const int mwo = fs.mword();   // the lane's word of a position's 8 mask words
     auto ctime = [&](const Tile& t, int cc, int to) { return col_time<MASKED>(t, cc, to, a.fn, a.d); };
     // g_v / g_u rows.  One-segment layouts shift the two column tiles by one row: they cover
     // image rows 2..65 (positions p0 + 1 .. p0 + 64, the right halo included), and rows 0 / 1
     // (p0 - 1, p0) are either the previous tile's rows 64 / 65 (the workgroup's previous tile is
     // the left neighbour in the same sub-sequence: copied, no MFMAs) or the halo tile's
-    // (one column block: lane i16 == 0 -> row 0, i16 == 1 -> row 1; lanes i16 >= 2 compute a copy
+    // (one column block: lane lc == 0 -> row 0, lc == 1 -> row 1; lanes lc >= 2 compute a copy
     // of row 0 and write it to unused row 66).  Other layouts: the tile's columns, no halo rows.
     // masked layouts have the one-segment geometry (row L = position p0 + L - 1, gathered) and
     // a tile may start / end inside a sub-sequence: the same halo rows, tap masks in g_a
@@ -144,13 +93,13 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
     // the next sub-sequence's first position, time q + 1)
     constexpr bool CARRY = ONESEG && !WHOLE && !MASKED;
     auto carry_of = [&](const Tile& t) { return CARRY && t.m0 + TMS >= a.n && t.p0 + TMS < a.T; };
-    int Lv[2][2];
+    int Lv[2][S::NCB];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) Lv[j][cb] = HALO ? Lc[j][cb] + 1 : Lc[j][cb];
-    const int Lh = i16 == 1 ? 1 : 0;
-    const int Lhw = i16 < 2 ? Lh : TMS + 2;
+        for (int cb = 0; cb < S::NCB; ++cb) Lv[j][cb] = HALO ? Lc[j][cb] + 1 : Lc[j][cb];
+    const int Lh = fs.lc == 1 ? 1 : 0;
+    const int Lhw = fs.lc < 2 ? Lh : TMS + 2;
 
     // ---- rows of the next tile: tot (-> split image) and D_l (-> residual) ----
     RowUnits<MASKED, ONESEG> ru;
@@ -207,42 +156,40 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
     // ---- relu-mask words (u16, position-indexed): u > 0 of the tile's columns and halos,
     //      e_l > 0 of its columns ----
     //      (per column half j and column block cb: the lane's word of its column)
-    uint32_t mu_c[2][2], muh_c = 0, me_c[2][2], mu_n[2][2], muh_n = 0, me_n[2][2], me_p[2] = {0u, 0u};
-    auto load_masks = [&](const Tile& t, uint32_t (&mu)[2][2], uint32_t& muh, uint32_t (&me)[2][2]) {
+    uint32_t mu_c[2][S::NCB], muh_c = 0, me_c[2][S::NCB], mu_n[2][S::NCB], muh_n = 0, me_n[2][S::NCB], me_p[S::NCB] = {};
+    auto load_masks = [&](const Tile& t, uint32_t (&mu)[2][S::NCB], uint32_t& muh, uint32_t (&me)[2][S::NCB]) {
         const size_t pb = (size_t)t.b * a.T + t.p0;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
+            for (int cb = 0; cb < S::NCB; ++cb) {
                 // u > 0 of the g_v rows Lv[j][cb]; a position past the clip reads any word (its
                 // tot row is zero)
-                const int c = 32 * j + 16 * cb + i16;
+                const int c = fs.col(j, cb);
                 const int pv = HALO ? min(t.p0 + 1 + c, a.T - 1) : t.p0 + c;
                 mu[j][cb] = a.mu[((size_t)t.b * a.T + pv) * 8 + mwo];
                 me[j][cb] = a.me[(pb + c) * 8 + mwo];
             }
         if (HALO) {     // rows 0 / 1: p0 - 1 (outside the clip at p0 == 0: its tot row is zero or tap-masked), p0
-            const int p = t.p0 + (i16 == 1 ? 0 : -1);
+            const int p = t.p0 + (fs.lc == 1 ? 0 : -1);
             muh = a.mu[((size_t)t.b * a.T + (p < 0 ? 0 : p)) * 8 + mwo];
         }
     };
 
     // ---- step 1: g_v of column half J (0, 1; 2 = the halo columns: column block 0 only).  Step
-    //      st = (K block st >> 1 of 32, column block st & 1); the halo GEMM's 4 steps carry two
-    //      side slots each ----
-    f32x4 acc1[3][4];
+    //      st of a column half = (K block S::skb(st), column block S::scb(st)); the halo GEMM
+    //      walks the K blocks of its one column block in 8 / NCB steps, which carry NCB side
+    //      slots each ----
+    typename S::Acc acc1[3];
     auto gemm1 = [&](auto j_tag, auto side) {
         constexpr int J = decltype(j_tag)::value;
-        constexpr int NS = J < 2 ? 8 : 4;
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc1[J][n][i] = 0.f;
+        constexpr int NS = J < 2 ? 8 : 8 / S::NCB;
+        S::zero(acc1[J]);
         uint4 bh[LA + 1], bl[LA + 1];
         auto bread = [&](int st, uint4& xh, uint4& xl) {
-            const int kb = J < 2 ? st >> 1 : st, cb = J < 2 ? st & 1 : 0;
+            const int kb = J < 2 ? S::skb(st) : st, cb = J < 2 ? S::scb(st) : 0;
             const int row = J < 2 ? Lv[J < 2 ? J : 0][cb] : Lh;
-            const uint8_t* p = XS + row * RS + kb * 64 + q4 * 16;
+            const uint8_t* p = fs.bfrag(XS + row * RS, kb);
             xh = lds16(p);
             xl = lds16(p + 256);
         };
@@ -250,69 +197,64 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
         for (int q = 0; q < LA; ++q) bread(q, bh[q], bl[q]);
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
-            const int kb = J < 2 ? st >> 1 : st, cb = J < 2 ? st & 1 : 0, bi = st % (LA + 1);
-            f32x4& c0 = acc1[J][2 * cb];
-            f32x4& c1 = acc1[J][2 * cb + 1];
-            c0 = mfma16(wr[2 * kb][0], bh[bi], c0);
-            c1 = mfma16(wr[2 * kb + 1][0], bh[bi], c1);
+            const int kb = J < 2 ? S::skb(st) : st, cb = J < 2 ? S::scb(st) : 0, bi = st % (LA + 1);
+            S::step_first(acc1[J], wr, kb, cb, bh[bi]);
             if (st + LA < NS) bread(st + LA, bh[(st + LA) % (LA + 1)], bl[(st + LA) % (LA + 1)]);
             if (J < 2) side(st);
-            else { side(2 * st); side(2 * st + 1); }
-            c0 = mfma16(wr[2 * kb][1], bh[bi], c0);
-            c1 = mfma16(wr[2 * kb + 1][1], bh[bi], c1);
-            c0 = mfma16(wr[2 * kb][0], bl[bi], c0);
-            c1 = mfma16(wr[2 * kb + 1][0], bl[bi], c1);
-            step6_schedule();
+            else { side(S::NCB * st); if (S::NCB > 1) side(S::NCB * st + 1); }   // (as a loop: other code)
+            S::step_rest(acc1[J], wr, kb, cb, bh[bi], bl[bi]);
         }
     };
-    // g_u of sub-tile (J, g) (rb = g & 1, cb = g >> 1; the halo tile: g < 2) in two parts: mask;
+    // g_u of unit (J, g) (the halo tile: the units of column block 0) in two parts: mask;
     // scale + split -> image row
     float4 gq = make_float4(0.f, 0.f, 0.f, 0.f);
-    int Lv1t[2] = {Lv[1][0], Lv[1][1]};   // rows of half 1 (a CARRY tile: its right-halo column 63 -> row 67)
+    // rows of half 1's first and last column block (a CARRY tile: its right-halo column 63 -> row
+    // 67); initialised as an aggregate: filled by a loop over NCB it compiles to other code
+    int Lv1t[2] = {Lv[1][0], Lv[1][S::NCB - 1]};
     auto gu_part = [&](int J, int g, int part, float f) {
-        const int rb = g & 1, cb = g >> 1;
+        const int rb = g & (UR - 1), cb = S::cb(g);
         if (part == 0) {
             const uint32_t wd_ = J < 2 ? mu_c[J < 2 ? J : 0][cb] : muh_c;
-            const int mg = mg0 + 2 * rb;
-            gq.x = keep_if(acc1[J][g][0], wd_, mg);
-            gq.y = keep_if(acc1[J][g][1], wd_, 4 + mg);
-            gq.z = keep_if(acc1[J][g][2], wd_, 8 + mg);
-            gq.w = keep_if(acc1[J][g][3], wd_, 12 + mg);
+            const int mg = mg0 + MGR * rb;
+            const f32x4 au = S::unit(acc1[J], g);
+            gq.x = keep_if(au[0], wd_, mg);
+            gq.y = keep_if(au[1], wd_, 4 + mg);
+            gq.z = keep_if(au[2], wd_, 8 + mg);
+            gq.w = keep_if(au[3], wd_, 12 + mg);
         } else {
             // the scale after the mask (f is a power of two: the same values), so that the
             // split's low half fuses with it into one v_fma_mix_f32
             uint32_t h01, l01, h23, l23;
             split2s(gq.x * f, gq.y * f, h01, l01);
             split2s(gq.z * f, gq.w * f, h23, l23);
-            uint8_t* p = XG + (J == 0 ? Lv[0][cb] : J == 1 ? Lv1t[cb] : Lhw) * RS + 2 * (chq + 16 * rb);
+            uint8_t* p = XG + (J == 0 ? Lv[0][cb] : J == 1 ? Lv1t[cb] : Lhw) * RS + 2 * (ch0 + CHR * rb);
             *reinterpret_cast<uint2*>(p) = make_uint2(h01, h23);
             *reinterpret_cast<uint2*>(p + 256) = make_uint2(l01, l23);
         }
     };
 
-    // ---- step 2: g_a of column half J; step st = (tap st >> 3, K block (st & 7) >> 1, column
-    //      block st & 1) ----
-    f32x4 acc2[2][4];
+    // ---- step 2: g_a of column half J; step st = (tap st >> 3, step st & 7 of the tap's K
+    //      pass: S::skb, S::scb) ----
+    typename S::Acc acc2[2];
     auto gemm2 = [&](auto j_tag, auto side, const Tile& cu) {
         constexpr int J = decltype(j_tag)::value;
-        bool ok0[2] = {true, true}, ok2[2] = {true, true};
+        bool ok0[S::NCB], ok2[S::NCB];
+#pragma unroll
+        for (int cb = 0; cb < S::NCB; ++cb) ok0[cb] = ok2[cb] = true;
         if (MASKED) {
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                const int pc = cu.p0 + 32 * J + 16 * cb + i16;
+            for (int cb = 0; cb < S::NCB; ++cb) {
+                const int pc = cu.p0 + fs.col(J, cb);
                 const int m = pc - (int)fdiv((uint32_t)pc, a.fn) * a.n;
                 ok0[cb] = m > 0;
                 ok2[cb] = m < a.n - 1;
             }
         }
-#pragma unroll
-        for (int n = 0; n < 4; ++n)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc2[J][n][i] = 0.f;
+        S::zero(acc2[J]);
         uint4 bh[LA + 1], bl[LA + 1];
         auto bread = [&](int st, uint4& xh, uint4& xl) {
-            const int tp = st >> 3, kb = (st & 7) >> 1, cb = st & 1;
-            const uint8_t* p = XG + (Lc[J][cb] + 1 - tp) * RS + kb * 64 + q4 * 16;
+            const int tp = st >> 3, s = st & 7;
+            const uint8_t* p = fs.bfrag(XG + (Lc[J][S::scb(s)] + 1 - tp) * RS, S::skb(s));
             xh = lds16(p);
             xl = lds16(p + 256);
         };
@@ -320,60 +262,54 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
         for (int q = 0; q < LA; ++q) bread(q, bh[q], bl[q]);
 #pragma unroll
         for (int st = 0; st < 24; ++st) {
-            const int tp = st >> 3, kb = (st & 7) >> 1, cb = st & 1, bi = st % (LA + 1);
+            const int tp = st >> 3, s = st & 7, cb = S::scb(s), bi = st % (LA + 1);
             uint4 xh = bh[bi], xl = bl[bi];
             if (MASKED && ((tp == 0 && !ok2[cb]) || (tp == 2 && !ok0[cb]))) {
                 xh = make_uint4(0, 0, 0, 0);
                 xl = xh;
             }
-            f32x4& c0 = acc2[J][2 * cb];
-            f32x4& c1 = acc2[J][2 * cb + 1];
-            c0 = mfma16(wd[tp][2 * kb][0], xh, c0);
-            c1 = mfma16(wd[tp][2 * kb + 1][0], xh, c1);
+            S::step_first(acc2[J], wd[tp], S::skb(s), cb, xh);
             if (st + LA < 24) bread(st + LA, bh[(st + LA) % (LA + 1)], bl[(st + LA) % (LA + 1)]);
             side(st);
-            c0 = mfma16(wd[tp][2 * kb][1], xh, c0);
-            c1 = mfma16(wd[tp][2 * kb + 1][1], xh, c1);
-            c0 = mfma16(wd[tp][2 * kb][0], xl, c0);
-            c1 = mfma16(wd[tp][2 * kb + 1][0], xl, c1);
-            step6_schedule();
+            S::step_rest(acc2[J], wd[tp], S::skb(s), cb, xh, xl);
         }
     };
 
-    // ---- epilogue unit (J, sub-tile g) of tile et in three parts: residual read; out -> HBM;
-    //      max (channels chq + 16 rb .. + 3 of column 16 cb + i16) ----
+    // ---- epilogue unit (J, g) of tile et in three parts: residual read; out -> HBM; max
+    //      (channels ch0 + S::choff(g) .. + 3 of the lane's column of column block S::cb(g)) ----
     float omax = 0.f, inv2p = 0.f;
-    float* dst[2] = {nullptr, nullptr};
+    float* dst[S::NCB] = {};
     rsrc_t rs_o;            // unmasked layouts: the stores through a resource at the tile's base time
-    uint32_t colo[2][2];
+    uint32_t colo[2][S::NCB];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) colo[j][cb] = (uint32_t)((toff[j][cb] * C + chq) * 4);
-    uint32_t ocol[2] = {0u, 0u};
+        for (int cb = 0; cb < S::NCB; ++cb) colo[j][cb] = (uint32_t)((toff[j][cb] * C + ch0) * 4);
+    uint32_t ocol[S::NCB] = {};
     float4 oe, oo;
-    float sk0 = 0.f, sk1 = 0.f, sk2 = 0.f;   // SX: the lane's dot products over its 8 channels of a column
-    size_t sxo[2] = {0, 0};                  // SX: spart float index of (column, wave)
+    float sk0 = 0.f, sk1 = 0.f, sk2 = 0.f;   // SX: the lane's dot products over its channels of a column
+    size_t sxo[S::NCB] = {};                 // SX: spart float index of (column, wave)
     auto epi_begin = [&](const Tile& et_, int J) {
         const Tile et = memt(et_);
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            const int c = 32 * J + 16 * cb + i16;
+        for (int cb = 0; cb < S::NCB; ++cb) {
+            const int c = fs.col(J, cb);
             if (SX) sxo[cb] = (((size_t)et.b * a.T + ctime(et, c, toff[J][cb])) * 4 + w) * 4;
-            else if (MASKED) dst[cb] = a.gout + ((size_t)et.b * a.T + ctime(et, c, toff[J][cb])) * C + chq;
+            else if (MASKED) dst[cb] = a.gout + ((size_t)et.b * a.T + ctime(et, c, toff[J][cb])) * C + ch0;
             else ocol[cb] = colo[J][cb];
         }
         if (!SX && !MASKED) rs_o = mk_rsrc(a.gout + ((size_t)et.b * a.T + et.tb) * C);
     };
-    auto epi_part = [&](int J, int g, int part, const uint8_t* er, const uint32_t (&mw)[2], float inv2) {
-        const int rb = g & 1, cb = g >> 1, ch = chq + 16 * rb, mg = mg0 + 2 * rb;
+    auto epi_part = [&](int J, int g, int part, const uint8_t* er, const uint32_t (&mw)[S::NCB], float inv2) {
+        const int rb = g & (UR - 1), cb = S::cb(g), ch = ch0 + CHR * rb, mg = mg0 + MGR * rb;
         if (part == 0) {
             oe = *reinterpret_cast<const float4*>(er + Lc[J][cb] * RS + 4 * ch);
         } else if (part == 1) {
-            oo.x = fmaf(keep_if(acc2[J][g][0], mw[cb], mg), inv2, oe.x);
-            oo.y = fmaf(keep_if(acc2[J][g][1], mw[cb], 4 + mg), inv2, oe.y);
-            oo.z = fmaf(keep_if(acc2[J][g][2], mw[cb], 8 + mg), inv2, oe.z);
-            oo.w = fmaf(keep_if(acc2[J][g][3], mw[cb], 12 + mg), inv2, oe.w);
+            const f32x4 au = S::unit(acc2[J], g);
+            oo.x = fmaf(keep_if(au[0], mw[cb], mg), inv2, oe.x);
+            oo.y = fmaf(keep_if(au[1], mw[cb], 4 + mg), inv2, oe.y);
+            oo.z = fmaf(keep_if(au[2], mw[cb], 8 + mg), inv2, oe.z);
+            oo.w = fmaf(keep_if(au[3], mw[cb], 12 + mg), inv2, oe.w);
             if (SX) {
                 const float4 q0 = *reinterpret_cast<const float4*>(&W0S[ch]);
                 const float4 q1 = *reinterpret_cast<const float4*>(&W0S[C + ch]);
@@ -381,15 +317,14 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
                 sk0 = fmaf(q0.w, oo.w, fmaf(q0.z, oo.z, fmaf(q0.y, oo.y, fmaf(q0.x, oo.x, sk0))));
                 sk1 = fmaf(q1.w, oo.w, fmaf(q1.z, oo.z, fmaf(q1.y, oo.y, fmaf(q1.x, oo.x, sk1))));
                 sk2 = fmaf(q2.w, oo.w, fmaf(q2.z, oo.z, fmaf(q2.y, oo.y, fmaf(q2.x, oo.x, sk2))));
-            } else if (MASKED) *reinterpret_cast<float4*>(dst[cb] + 16 * rb) = oo;
-            else bst4(rs_o, ocol[cb] + 64 * rb, 0u, oo);
+            } else if (MASKED) *reinterpret_cast<float4*>(dst[cb] + CHR * rb) = oo;
+            else bst4(rs_o, ocol[cb] + 4 * CHR * rb, 0u, oo);
         } else {
             omax = fmaxf(omax, fmaxf(fmaxf(fabsf(oo.x), fabsf(oo.y)), fmaxf(fabsf(oo.z), fabsf(oo.w))));
-            if (SX && rb == 1) {   // the column's 8 channels of this lane done: + the other 3 lane quads' -> spart
-                float t0 = sk0 + __shfl_xor(sk0, 16), t1 = sk1 + __shfl_xor(sk1, 16), t2 = sk2 + __shfl_xor(sk2, 16);
-                t0 += __shfl_xor(t0, 32); t1 += __shfl_xor(t1, 32); t2 += __shfl_xor(t2, 32);
-                if (q4 == 0)
-                    *reinterpret_cast<float4*>(a.spart + sxo[cb]) = make_float4(t0, t1, t2, 0.f);
+            if (SX && rb == UR - 1) {   // the column's channels of this lane done: + the other lanes' of the column -> spart
+                fs.col_sum(sk0, sk1, sk2);
+                if (fs.lk == 0)
+                    *reinterpret_cast<float4*>(a.spart + sxo[cb]) = make_float4(sk0, sk1, sk2, 0.f);
                 sk0 = sk1 = sk2 = 0.f;
             }
         }
@@ -454,7 +389,8 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
         const bool cont = HALO && !FIRST && prv.b == cu.b && prv.p0 + TMS == cu.p0 && (MASKED || CARRY || cu.m0 != 0);
         const bool fos = CARRY && cu.m0 == 0;
         const bool cry = carry_of(cu);
-        Lv1t[1] = cry && i16 == 15 ? GROWS - 1 : Lv[1][1];   // column 63: half 1, block 1, i16 15
+        // column 63: the last lane column of half 1's last column block
+        Lv1t[S::NCB - 1] = cry && fs.col(1, S::NCB - 1) == TMS - 1 ? GROWS - 1 : Lv[1][S::NCB - 1];
         const int cpo = ((lane >> 2) & 1) * 256 + 64 * w + 16 * (lane & 3);   // (side work of A)
         const int csr = fos ? ((lane >> 3) ? GROWS - 1 : TMS) : TMS + (lane >> 3);
         uint4 cpv = make_uint4(0, 0, 0, 0);
@@ -485,7 +421,7 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
             // H: g_v of rows 0 / 1 + g_u of half 1; then g_u of rows 0 / 1
             gemm1(J2{}, [&](int kb) { gu_part(1, kb >> 1, kb & 1, f_u); });
 #pragma unroll
-            for (int q = 0; q < 4; ++q) gu_part(2, q >> 1, q & 1, f_u);
+            for (int q = 0; q < 8 / S::NCB; ++q) gu_part(2, q >> 1, q & 1, f_u);
         } else {
 #pragma unroll
             for (int q = 0; q < 8; ++q) gu_part(1, q >> 1, q & 1, f_u);
@@ -513,7 +449,7 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
         prv = cu;
         inv2p = inv2;
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
+        for (int cb = 0; cb < S::NCB; ++cb) {
             me_p[cb] = me_c[1][cb];
             me_c[0][cb] = me_n[0][cb]; me_c[1][cb] = me_n[1][cb];
             mu_c[0][cb] = mu_n[0][cb]; mu_c[1][cb] = mu_n[1][cb];
@@ -535,30 +471,3 @@ __global__ void __launch_bounds__(FT, 1) k_block_bwd_s16(BwdArgsS a, Layout) {
     STAMP(12)
     STAMP_FLUSH(a.stamps)
 }
-
-}  // namespace
-
-void launch_block_bwd_s16(const BwdArgsS& a0, hipStream_t s) {
-    BwdArgsS a = a0;
-    a.fn = make_fdiv((uint32_t)a.n);
-    a.ft = make_fdiv((uint32_t)(SW_TILE_INTERLEAVE ? a.B : a.T / TMS));
-    const int nt = a.B * (a.T / TMS);
-    const dim3 grid(std::min(nt, a.cus > 0 ? std::min(a.cus, sw::num_cus()) : sw::num_cus()));
-    Layout ly;
-    const bool masked = pick_layout(a.n, ly);
-    const bool oneseg = !masked && ly.M == TMS;
-    if (a.spart && (!oneseg || a.dadd || a.d != 1)) { fprintf(stderr, "block_bwd_s: spart needs d = 1, no D\n"); abort(); }
-    const bool whole = oneseg && a.n == TMS;
-#define BWD_LAUNCH(M, O, D, X, W) hipLaunchKernelGGL((k_block_bwd_s16<M, O, D, X, W>), grid, dim3(FT), 0, s, a, ly)
-    if (masked) { if (a.dadd) BWD_LAUNCH(true, false, true, false, false); else BWD_LAUNCH(true, false, false, false, false); }
-    else if (whole && !a.spart) {
-        if (a.dadd) BWD_LAUNCH(false, true, true, false, true); else BWD_LAUNCH(false, true, false, false, true);
-    } else if (oneseg) {
-        if (a.dadd) BWD_LAUNCH(false, true, true, false, false);
-        else if (a.spart) BWD_LAUNCH(false, true, false, true, false);
-        else BWD_LAUNCH(false, true, false, false, false);
-    } else { if (a.dadd) BWD_LAUNCH(false, false, true, false, false); else BWD_LAUNCH(false, false, false, false, false); }
-#undef BWD_LAUNCH
-}
-
-}  // namespace ast

@@ -170,7 +170,7 @@ struct BwdArgsC {
 //   wrb [4 w][8 kb][2 hl][64]:                                     W_r[32 w + m][16 kb + 8 h + e]
 //   wdb [4 w][3 tap][8 kb][2 hl][64]:                              W_d[tap][32 w + m][16 kb + 8 h + e]
 // For the 16x16x32 kernels (k_block_fwd_s16 of block_fwd_split.hip, k_block_bwd_s16 of
-// block_bwd_split16.hip; ASTYLE_MFMA16
+// block_bwd_split.hip; ASTYLE_MFMA16
 // picks the form per direction, the default 2: the backward on 16x16x32, the forward on 32x32x16)
 // a direction's arrays hold 16x16x32 A fragments, slot s = 2 kb + rb (K block kb of 32, row block rb), lane (i, q) = (lane & 15, lane >> 4):
 //   wdf: W_d[tap][32 kb + 8 q + e][32 w + 16 rb + i]     wrf: W_r[32 kb + 8 q + e][32 w + 16 rb + i]

@@ -250,7 +250,7 @@ __device__ __forceinline__ f32x16 mfma_f16(uint4 a, uint4 b, f32x16 c) {
 }
 
 // ---- the 16x16x32 form (k_block_fwd_s16 in block_fwd_split.hip, k_block_bwd_s16 in
-//      block_bwd_split16.hip; ASTYLE_MFMA16 picks the form per direction; shipped, mode 2: the
+//      block_bwd_split.hip; ASTYLE_MFMA16 picks the form per direction; shipped, mode 2: the
 //      backward runs on it, 0.3-1.2 % faster per launch than on 32x32x16, the forward stays on
 //      32x32x16, where 16x16x32 is 4-5 % slower; round 6).  A wave's output tile of
 //      a column half is its 32 channels x 32 columns as four 16 x 16 sub-tiles n = 2 cb + rb (row
@@ -283,8 +283,8 @@ __device__ __forceinline__ void step6_schedule() {
 __device__ __forceinline__ uint32_t mask16(uint32_t w) { return (w | (w >> 12)) & 0xffffu; }
 
 // ---- fragment shapes: what a block kernel body written once for both MFMA forms
-//      (block_fwd_split_body.h) needs to know about the form.  A wave's output of a column half
-//      (its 32 channels x 32 columns) is NCB column blocks; a lane holds, per column half, four
+//      (block_fwd_split_body.h, block_bwd_split_body.h) needs to know about the form.  A wave's
+//      output of a column half (its 32 channels x 32 columns) is NCB column blocks; a lane holds, per column half, four
 //      units g of 4 consecutive channels of one column (element k of unit g: column col(j, cb(g)),
 //      channel ch0() + choff(g) + k, bit 4 k + mg0() + mgoff(g) of the column's mask word,
 //      common.h mbit).  A K pass over the 128 input channels is 8 steps s = (K block skb(s),
@@ -309,6 +309,10 @@ struct Frag32 {   // v_mfma_f32_32x32x16_f16: lane = (lc = lane & 31, lk = lane 
     static __device__ __forceinline__ int mgoff(int g) { return g; }
     static __device__ __forceinline__ bool col_done(int g) { return g == 3; }     // last unit of its column
     static __device__ __forceinline__ float el(const Acc& a, int g, int k) { return a[4 * g + k]; }
+    // unit g's four elements at once (the backward body; the 16x16x32 form's own vector)
+    static __device__ __forceinline__ f32x4 unit(const Acc& a, int g) {
+        return f32x4{a[4 * g], a[4 * g + 1], a[4 * g + 2], a[4 * g + 3]};
+    }
     static __device__ __forceinline__ void zero(Acc& a) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) a[i] = 0.f;
@@ -330,6 +334,11 @@ struct Frag32 {   // v_mfma_f32_32x32x16_f16: lane = (lc = lane & 31, lk = lane 
     // a column's 8 u16 mask words: the lane holds all four groups of word 4 lk + w of its column
     __device__ __forceinline__ uint32_t col_word(uint32_t m) const { return m; }   // the finished word
     static constexpr bool ALL_WRITE = true;   // every lane writes its word
+    __device__ __forceinline__ int mword() const { return 4 * lk + w; }            // the word the lane reads
+    // sums over the lanes of a column (the backward's SX dot products; the lanes lk == 0 write them)
+    static __device__ __forceinline__ void col_sum(float& s0, float& s1, float& s2) {
+        s0 += __shfl_xor(s0, 32); s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
+    }
 };
 struct Frag16 {   // v_mfma_f32_16x16x32_f16 (above): lane = (lc = lane & 15, lk = lane >> 4)
     typedef f32x4 Acc[4];   // unit g = sub-tile 2 cb + rb: channels 16 rb + 4 lk .. + 3
@@ -345,6 +354,7 @@ struct Frag16 {   // v_mfma_f32_16x16x32_f16 (above): lane = (lc = lane & 15, lk
     static __device__ __forceinline__ int mgoff(int g) { return 2 * (g & 1); }
     static __device__ __forceinline__ bool col_done(int g) { return (g & 1) == 1; }
     static __device__ __forceinline__ float el(const Acc& a, int g, int k) { return a[g][k]; }
+    static __device__ __forceinline__ f32x4 unit(const Acc& a, int g) { return a[g]; }
     static __device__ __forceinline__ void zero(Acc& a) {
 #pragma unroll
         for (int n = 0; n < 4; ++n)
@@ -372,6 +382,11 @@ struct Frag16 {   // v_mfma_f32_16x16x32_f16 (above): lane = (lc = lane & 15, lk
     // apart); the quads 0 / 1 write it
     __device__ __forceinline__ uint32_t col_word(const uint32_t& m) const { return m | (uint32_t)__shfl_xor((int)m, 32); }
     static constexpr bool ALL_WRITE = false;  // the lane quads lk < 2 write the words 4 lk + w
+    __device__ __forceinline__ int mword() const { return 4 * (lk & 1) + w; }
+    static __device__ __forceinline__ void col_sum(float& s0, float& s1, float& s2) {
+        s0 += __shfl_xor(s0, 16); s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
+        s0 += __shfl_xor(s0, 32); s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
+    }
 };
 
 // tied no-op: pins a fragment to the accumulator register file (MFMA A operands may be AGPRs)

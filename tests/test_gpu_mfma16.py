@@ -1,6 +1,9 @@
 """GPU: the 16x16x32 form of the split block kernels (ASTYLE_MFMA16=1 both, k_block_fwd_s16 of
-block_fwd_split.hip / block_bwd_split16.hip, round 6; the default 2 runs the backward on it, the forward on 32x32x16):
-the golden loss / gradient against the fp64 oracle at the split mode's bars, agreement with the
+block_fwd_split.hip / k_block_bwd_s16 of block_bwd_split.hip, round 6; the default 2 runs the backward on it, the
+forward on 32x32x16):
+the golden loss / gradient against the fp64 oracle at the split mode's bars ('ours', every tensor
+style-tapped, and 'trunc' of test_gpu_split.py, few taps: the backward kernels without a direct
+gradient term run too), agreement with the
 32x32x16 kernels (ASTYLE_MFMA16=0) to fp32 rounding (the K accumulation
 order differs, so not bit for bit), and bit-exact batch invariance (a clip alone equals the same
 clip in slot 2 of 4).  The knob is read once per process, so each setting runs in a child."""
@@ -27,6 +30,19 @@ e = StyleEngine(1, 2048, [25], list(range(30)), precision='split', device=dev, l
 e.set_targets(torch.tensor(tg['ours_phi_c']), torch.tensor(tg['ours_phi_s']))
 p, gr = e.loss_grad(torch.tensor(g['ours_x'][None], dtype=torch.float32, device=dev))
 out = {'parts': p[0].cpu().tolist(), 'grad': gr[0].cpu().double().numpy().tolist()}
+e.close()
+# 'trunc' (test_gpu_split.CASES; targets as test_gpu_split._targets builds them, the golden file's weights)
+from oracle import astyle_oracle as O
+from audio_style_transfer_amd.weights import synthetic_clips, synthetic_weights
+kw = dict(cont_ids=[25, 31], style_ids=[3, 7], gatys=False, nb_channels=64, cnt_channels=16)
+wts = synthetic_weights(0)
+xc, xs = (O.mu_law_numpy(synthetic_clips(1, 2048, seed)[0]) for seed in (1000, 5000))
+phi_c, phi_s = O.targets_from_audio(wts, xc, [xs], [xc], **kw)
+e = StyleEngine(1, 2048, kw['cont_ids'], kw['style_ids'], cnt_channels=kw['cnt_channels'],
+                nb_channels=kw['nb_channels'], gatys=kw['gatys'], weights=wts, precision='split', device=dev)
+e.set_targets(torch.tensor(phi_c, dtype=torch.float32), torch.tensor(phi_s, dtype=torch.float32))
+p, gr = e.loss_grad(torch.tensor(g['trunc_x'][None], dtype=torch.float32, device=dev))
+out['trunc_parts'], out['trunc_grad'] = p[0].cpu().tolist(), gr[0].cpu().double().numpy().tolist()
 e.close()
 # batch invariance at T = 4096: clip 6 alone and in slot 2 of clips 4..7
 res = []
@@ -62,6 +78,9 @@ def test_mfma16_kernels_match_the_oracle_and_the_default_kernels():
     for o in (a, b):
         assert abs(o['parts'][0] - ref_p[0]) <= 1e-4 * abs(ref_p[0])
         assert rel(o['grad'], ref_g) <= 2e-3
+        for k in range(4):
+            assert abs(o['trunc_parts'][k] - g['trunc_parts'][k]) <= 1e-4 * abs(g['trunc_parts'][k]) + 1e-7, (k, o['trunc_parts'])
+        assert rel(o['trunc_grad'], g['trunc_grad']) <= 2e-3
     assert abs(a['parts'][0] - b['parts'][0]) <= 1e-5 * abs(b['parts'][0])
     # bit-exact batch invariance of the 16x16x32 kernels
     assert a['alone'][0] == a['slot'][0] and a['alone'][1] == a['slot'][1]

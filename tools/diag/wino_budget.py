@@ -64,14 +64,17 @@ def compile_res(path):
 def main():
     out = []
     with tempfile.TemporaryDirectory() as d:
+        # the kernels' text is the body file each .hip includes once per MFMA form: the probe is the
+        # .hip next to a patched copy of its body (an include in quotes looks there first)
         for f, wsrc in (('block_fwd_split.hip', 'wdf'), ('block_bwd_split.hip', 'wdb')):
-            src = open(os.path.join(CSRC, f)).read()
+            body = f[:-4] + '_body.h'
+            src = open(os.path.join(CSRC, body)).read()
             assert src.count('    pin_all(wd, wr);\n') == 1 and src.count('    STAMP_FLUSH(a.stamps)\n') == 1
             probe = src.replace('    pin_all(wd, wr);\n', '    pin_all(wd, wr);\n' + EXTRA_IN.replace('WSRC', wsrc))
             probe = probe.replace('    STAMP_FLUSH(a.stamps)\n', EXTRA_OUT + '    STAMP_FLUSH(a.stamps)\n')
-            pa, pb = os.path.join(d, f), os.path.join(d, 'wino_' + f)
-            open(pa, 'w').write(src)
-            open(pb, 'w').write(probe)
+            pa, pb = os.path.join(CSRC, f), os.path.join(d, f)
+            open(pb, 'w').write(open(pa).read())
+            open(os.path.join(d, body), 'w').write(probe)
             base = compile_res(pa)
             wino = compile_res(pb)
             for a, b in zip(base, wino):
