@@ -9,7 +9,7 @@
 //
 // Per (clip, time chunk, 32-channel group) workgroup, 8 waves x 4 channels, stages of 16 time
 // rows; the next two stages' global loads (128 KiB per workgroup) are in flight while a stage
-// computes:
+// computes (forward: three by default, and 8- / 4-channel workgroups at few clips):
 //   fwd  G_c = E_c E_c^T      v_mfma_f32_32x32x16_bf16, A = B fragments (lane (u, h):
 //                             E_u[t0 + 8 h .. + 8][c]) from an LDS image [c][u][hi t | lo t]
 //   bwd  D_c = S~_c E_c       v_mfma_f32_16x16x32_bf16 (A = S~_c halves in registers, B: lane
@@ -18,6 +18,20 @@
 //                             tensors and leaves as whole 128-B lines (+ the content grad: a
 //                             cg buffer, or the fused content tap computed here)
 // Loads and stores move whole 128-B lines (8 lanes x 16 B per row).
+//
+// The four forward kernels (k_gram_fwd_s / _n split, k_gram_fwd_f / _fn fp32) are one body,
+// gram_fwd_body.h, included inside each kernel with an arithmetic (GramSplit / GramF32 below), the
+// channels per workgroup (32 wide; 8, 4 narrow) and the ring depth.  Against the four kernels
+// written out (tools/diag/isa_compare.py --sources 'gram_split*.hip'): the six split
+// instantiations (k_gram_fwd_s<2>, <3>, k_gram_fwd_n<2, 4>, <3, 4>, <2, 8>, <3, 8>) and all 14
+// backward kernels are equal in instruction text and descriptor values; the fp32 pair took the
+// split kernels' loop (ring of 2, clamped unconditional loads, whole rings then the remainder) and
+// differs: k_gram_fwd_f 174 -> 170 VGPRs, k_gram_fwd_fn 130 -> 123, no spill, no scratch, LDS
+// 81920 B as before.  The places in the text that decide the shipped split kernels' code: the body
+// inside the __global__ function, not called from it; every image and gpart pointer formed in the
+// body, the second image operand read at a pointer offset (row + R1), not at a second index; the
+// wave's first channel formed once (wc) and the channel as c0 + wc + cc; the workgroup decoded
+// through decode() in the wide kernels and in place in the narrow ones.
 #include "common.h"
 #include <cstdlib>
 #include <cstdio>
@@ -65,170 +79,120 @@ __device__ __forceinline__ void split8(const float4 (&v)[8], uint4& hi, uint4& l
     lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
 
-// forward.  Staging: thread (w, l) loads tensor u = 8 (w & 3) + (l & 7), channel quad l >> 3,
-// rows t0 + 8 (w >> 2) + k (k = 0..7): one load instruction covers 8 whole lines.
-// NST stages of loads in flight (2: 128 KiB per workgroup; 3: 192 KiB, the registers of a
-// third stage fit beside the accumulators at the same two waves per SIMD)
+// ---- forward: one body (gram_fwd_body.h), two arithmetics, three geometries ----
+// An arithmetic fixes the image element and row stride; how a thread's 8 loaded float4 (4 channels
+// x 8 rows of one tensor) become each channel's two 16-B image pieces (written at row + 0 and
+// row + P1); where in a channel-stage image [u][16 rows] (first row ro) a lane reads its two
+// 16-B operands (at and at + R1); the MFMA sequence on them; the accumulator and its gpart store
+// place in gpart (gat / gval).  Its functions take registers and indices only: the body forms
+// every image and gpart pointer itself (a pointer passed through a function parameter compiles
+// to other address code in the shipped kernels).
+constexpr int GFN = 64;       // rows per narrow fill (4 stages)
+constexpr int FRF = 20;       // fp32 fwd image [c][u][t] row stride (floats): 80 B
+
+// split bf16 on v_mfma_f32_32x32x16_bf16: image row [hi 16 | lo 16 | pad 8]; A = B fragments, lane
+// (r, h): E_r[8 h .. + 8] of the stage as hi / lo; xh xh + xh xl + xl xh
+struct GramSplit {
+    typedef u16 elem;
+    typedef uint4 piece;
+    typedef f32x16 acc_t;
+    static constexpr int RS = FRS, P1 = 16, R1 = 16;
+    struct lane_t {
+        int r, h;
+        __device__ __forceinline__ lane_t(int lane) : r(lane & 31), h(lane >> 5) {}
+    };
+    static __device__ __forceinline__ void zero(acc_t& c) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) c[i] = 0.f;
+    }
+    static __device__ __forceinline__ void cut(const float4 (&v)[8], piece (&hi)[4], piece (&lo)[4]) {
+        split8<0>(v, hi[0], lo[0]);
+        split8<1>(v, hi[1], lo[1]);
+        split8<2>(v, hi[2], lo[2]);
+        split8<3>(v, hi[3], lo[3]);
+    }
+    static __device__ __forceinline__ int at(const lane_t& l, int ro) { return (ro + l.r) * FRS + 8 * l.h; }
+    static __device__ __forceinline__ void mma(const piece& xh, const piece& xl, acc_t& c) {
+        c = mfma_bf16(xh, xh, c);
+        c = mfma_bf16(xh, xl, c);
+        c = mfma_bf16(xl, xh, c);
+    }
+    // the lane's i-th Gram element (C/D map of 32x32x16) and its place in the 32 x 32 partial
+    static __device__ __forceinline__ int gat(const lane_t& l, int i) { return ((i & 3) + 8 * (i >> 2) + 4 * l.h) * 32 + l.r; }
+    static __device__ __forceinline__ float gval(const acc_t& c, int i) { return c[i]; }
+};
+
+// fp32 on v_mfma_f32_16x16x4f32: image row [t] fp32 (conflict-free 16-B reads); the symmetric Gram
+// as three tiles (U0 U0, U0 U1, U1 U1; U = 16 tensors) per k-step, the fourth written as the
+// mirror of (U0, U1): 3/4 of the MFMA cycles of one 32x32 tile.  Lane (i16, kq) supplies tensors
+// i16 and 16 + i16 at rows 4 kq .. 4 kq + 3 (k-step s takes row 4 kq + s: any common permutation
+// of K is the same Gram) for A and B alike
+struct GramF32 {
+    typedef float elem;
+    typedef float4 piece;
+    struct acc_t { f32x4 t[3]; };   // Gram tiles (U0, U0), (U0, U1), (U1, U1); (U1, U0) = mirror
+    static constexpr int RS = FRF, P1 = 4, R1 = 16 * FRF;
+    struct lane_t {
+        int i16, kq;
+        __device__ __forceinline__ lane_t(int lane) : i16(lane & 15), kq(lane >> 4) {}
+    };
+    static __device__ __forceinline__ void zero(acc_t& c) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) c.t[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    static __device__ __forceinline__ void cut(const float4 (&v)[8], piece (&p0)[4], piece (&p1)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {   // channel j: rows 0..3, rows 4..7
+            auto e = [&](int k) { return j == 0 ? v[k].x : j == 1 ? v[k].y : j == 2 ? v[k].z : v[k].w; };
+            p0[j] = make_float4(e(0), e(1), e(2), e(3));
+            p1[j] = make_float4(e(4), e(5), e(6), e(7));
+        }
+    }
+    static __device__ __forceinline__ int at(const lane_t& l, int ro) { return ro * FRF + 4 * l.kq + l.i16 * FRF; }
+    static __device__ __forceinline__ void mma(const piece& u0, const piece& u1, acc_t& c) {
+        const float a0[4] = {u0.x, u0.y, u0.z, u0.w}, a1[4] = {u1.x, u1.y, u1.z, u1.w};
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            c.t[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[st], a0[st], c.t[0], 0, 0, 0);
+            c.t[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[st], a1[st], c.t[1], 0, 0, 0);
+            c.t[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[st], a1[st], c.t[2], 0, 0, 0);
+        }
+    }
+    // the lane's i-th Gram element and its place: element i & 3 of tile (i >> 2 = 0: (U0, U0); 1, 2:
+    // (U0, U1) and its mirror; 3: (U1, U1)); a tile's lane holds [4 kq + i][i16] (C/D map of 16x16x4)
+    static __device__ __forceinline__ int gat(const lane_t& l, int i) {
+        const int rr = 4 * l.kq + (i & 3), q = i >> 2;
+        return q == 0 ? rr * 32 + l.i16 : q == 1 ? rr * 32 + 16 + l.i16 : q == 2 ? (16 + l.i16) * 32 + rr : (16 + rr) * 32 + 16 + l.i16;
+    }
+    static __device__ __forceinline__ float gval(const acc_t& c, int i) { return c.t[(i >> 2) - (i >> 3)][i & 3]; }
+};
+
+// The kernels: names and template parameters as the launchers, profiles and tools know them.
+// Each names the arithmetic A, NCH channels per workgroup (32: the wide geometry; 8, 4: the narrow
+// ones for few clips) and NRING fills of loads in flight, and includes the one body
+// (gram_fwd_body.h: the geometries, the ring of loads and why the body is not a function).
 template <int NST>
 __global__ void __launch_bounds__(GWT) k_gram_fwd_s(GramArgs a) {
-    __shared__ __attribute__((aligned(16))) u16 I[GCS * 32 * FRS];   // [c][u][hi t | lo t]
-    int b, ch, c0;
-    decode(a, b, ch, c0);
-    const int tlen = a.T / a.nchunk, tbeg = ch * tlen;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int su = 8 * (w & 3) + (lane & 7), sq = lane >> 3, tb = w >> 2;
-    const bool real = su < a.nu;
-    const float* src = real ? (const float*)a.act + (size_t)a.uid[su] * a.tstride +
-                              (size_t)b * a.T * C + c0 + 4 * sq + (size_t)8 * tb * C
-                            : (const float*)a.zero16;
-    const size_t rs = real ? C : 0;
-    f32x16 acc[4];
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[cc][i] = 0.f;
-    // NST stages of loads in flight (a ring of NST register sets; tlen is a multiple of 2 GSS).
-    // Every load is unconditional (past the chunk a stage re-reads the chunk's last rows, an L2
-    // hit) and the loop runs whole rings, the remainder after it: a conditional load made the
-    // compiler copy the ring registers (v_mov) behind vmcnt(0) waits, so no stage stayed in
-    // flight across a stage
-    float4 v[NST][8];
-    const int tend = tbeg + tlen;
-    auto load = [&](float4 (&v)[8], int t0) {
-        const int tr = min(t0, tend - GSS);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float4*>(src + (size_t)(tr + k) * rs);
-    };
-    auto stage = [&](float4 (&v)[8], int t0) {
-        uint4 fh[4], fl[4];          // channel 4 sq + j: 8 consecutive rows, hi / lo
-        split8<0>(v, fh[0], fl[0]);
-        split8<1>(v, fh[1], fl[1]);
-        split8<2>(v, fh[2], fl[2]);
-        split8<3>(v, fh[3], fl[3]);
-        load(v, t0 + NST * GSS);
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            u16* row = &I[((4 * sq + j) * 32 + su) * FRS + 8 * tb];
-            *reinterpret_cast<uint4*>(row) = fh[j];
-            *reinterpret_cast<uint4*>(row + 16) = fl[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            const u16* row = &I[((4 * w + cc) * 32 + r) * FRS + 8 * h];
-            const uint4 xh = *reinterpret_cast<const uint4*>(row);
-            const uint4 xl = *reinterpret_cast<const uint4*>(row + 16);
-            acc[cc] = mfma_bf16(xh, xh, acc[cc]);
-            acc[cc] = mfma_bf16(xh, xl, acc[cc]);
-            acc[cc] = mfma_bf16(xl, xh, acc[cc]);
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < NST; ++q) load(v[q], tbeg + q * GSS);
-    const int nst = tlen / GSS, nring = nst / NST;
-    int t0 = tbeg;
-    for (int i = 0; i < nring; ++i, t0 += NST * GSS) {
-#pragma unroll
-        for (int q = 0; q < NST; ++q) stage(v[q], t0 + q * GSS);
-    }
-#pragma unroll
-    for (int q = 0; q < NST - 1; ++q)
-        if (q < nst - nring * NST) stage(v[q], t0 + q * GSS);
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) {
-        float* dst = a.gpart + (((size_t)b * a.nchunk + ch) * C + c0 + 4 * w + cc) * 1024;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dst[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = acc[cc][i];
-    }
+    using A = GramSplit;
+    constexpr int NCH = GCS, NRING = NST;
+#include "gram_fwd_body.h"
 }
-
-// forward for few clips (k_gram_fwd_n): 8 channels per workgroup instead of 32, so a clip's
-// chunk spreads over 16 workgroups instead of 4 (one clip: 64 instead of 16).  Wave w owns
-// channel c0 + w and runs, stage by stage (16 rows), the same three MFMAs on the same
-// fragments as k_gram_fwd_s's wave for that channel: the partials are bit-identical, so a
-// clip's result does not depend on which kernel the batch size selects.  Staging: a fill is 4
-// stages (64 rows); thread (w, l) loads tensor 8 (w & 3) + (l & 7), channel quad (l >> 3) & 1,
-// rows 8 g .. + 8 of the fill, g = (l >> 4) + 4 (w >> 2); two fills of loads in flight.
-constexpr int GCN = 8;        // channels per narrow forward workgroup
-constexpr int GFN = 64;       // rows per narrow fill (4 stages)
-// NFL fills of loads in flight in a ring (round 6; 2 before, with a conditional load that, as in
-// the round-5 wide kernels, made the compiler drain the ring at every fill).  Loads are
-// unconditional: past the chunk a fill re-reads the chunk's last fill (an L2 hit); the loop runs
-// whole rings, the remainder after it.  The MFMA sequence per channel is unchanged (same bits).
-// NC channels per workgroup, one wave each (8; 4 for a single clip: twice the workgroups, 16-B row
-// pieces).  Staging, NC = 8: thread (w, l) loads tensor 8 (w & 3) + (l & 7), channel quad
-// (l >> 3) & 1, rows 8 g .. + 8 of the fill, g = (l >> 4) + 4 (w >> 2); NC = 4: tensor 8 w + (l & 7),
-// channel quad 0, g = l >> 3
-template <int NFL, int NC>
+template <int NFL, int NC>   // NC = 8; 4 for a single clip (twice the workgroups)
 __global__ void __launch_bounds__(64 * NC) k_gram_fwd_n(GramArgs a) {
-    __shared__ __attribute__((aligned(16))) u16 I[(GFN / GSS) * NC * 32 * FRS];   // [stage][c][u][hi | lo]
-    constexpr int ncg = C / NC;
-    const int nwg = a.B * a.nchunk * ncg;
-    int work = xcd_remap(blockIdx.x, nwg);
-    const int cgi = work % ncg; work /= ncg;
-    const int ch = work % a.nchunk, b = work / a.nchunk, c0 = cgi * NC;
-    const int tlen = a.T / a.nchunk, tbeg = ch * tlen, tend = tbeg + tlen;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int su = NC == 8 ? 8 * (w & 3) + (lane & 7) : 8 * w + (lane & 7);
-    const int sq = NC == 8 ? (lane >> 3) & 1 : 0;
-    const int g = NC == 8 ? (lane >> 4) + 4 * (w >> 2) : lane >> 3;
-    const bool real = su < a.nu;
-    const float* src = real ? (const float*)a.act + (size_t)a.uid[su] * a.tstride +
-                              (size_t)b * a.T * C + c0 + 4 * sq + (size_t)8 * g * C
-                            : (const float*)a.zero16;
-    const size_t rs = real ? C : 0;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float4 v[NFL][8];
-    auto load = [&](float4 (&vv)[8], int t0) {
-        const int tr = min(t0, tend - GFN);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) vv[k] = *reinterpret_cast<const float4*>(src + (size_t)(tr + k) * rs);
-    };
-    auto fill = [&](float4 (&vv)[8], int t0) {
-        uint4 fh[4], fl[4];
-        split8<0>(vv, fh[0], fl[0]);
-        split8<1>(vv, fh[1], fl[1]);
-        split8<2>(vv, fh[2], fl[2]);
-        split8<3>(vv, fh[3], fl[3]);
-        load(vv, t0 + NFL * GFN);
-        __syncthreads();   // the previous fill's MFMA reads are done
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // stage g >> 1, channel 4 sq + j, tensor su; rows 8 (g & 1) .. of the stage
-            u16* row = &I[(((g >> 1) * NC + 4 * sq + j) * 32 + su) * FRS + 8 * (g & 1)];
-            *reinterpret_cast<uint4*>(row) = fh[j];
-            *reinterpret_cast<uint4*>(row + 16) = fl[j];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int st = 0; st < GFN / GSS; ++st) {
-            const u16* row = &I[((st * NC + w) * 32 + r) * FRS + 8 * h];
-            const uint4 xh = *reinterpret_cast<const uint4*>(row);
-            const uint4 xl = *reinterpret_cast<const uint4*>(row + 16);
-            acc = mfma_bf16(xh, xh, acc);
-            acc = mfma_bf16(xh, xl, acc);
-            acc = mfma_bf16(xl, xh, acc);
-        }
-    };
-#pragma unroll
-    for (int q = 0; q < NFL; ++q) load(v[q], tbeg + q * GFN);
-    const int nf = tlen / GFN, nring = nf / NFL;
-    int t0 = tbeg;
-    for (int i = 0; i < nring; ++i, t0 += NFL * GFN) {
-#pragma unroll
-        for (int q = 0; q < NFL; ++q) fill(v[q], t0 + q * GFN);
-    }
-#pragma unroll
-    for (int q = 0; q < NFL - 1; ++q)
-        if (q < nf - nring * NFL) fill(v[q], t0 + q * GFN);
-    float* dst = a.gpart + (((size_t)b * a.nchunk + ch) * C + c0 + w) * 1024;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dst[((i & 3) + 8 * (i >> 2) + 4 * h) * 32 + r] = acc[i];
+    using A = GramSplit;
+    constexpr int NCH = NC, NRING = NFL;
+#include "gram_fwd_body.h"
+}
+constexpr int GCN = 8;        // channels per fp32 narrow forward workgroup
+__global__ void __launch_bounds__(GWT) k_gram_fwd_f(GramArgs a) {
+    using A = GramF32;
+    constexpr int NCH = GCS, NRING = 2;
+#include "gram_fwd_body.h"
+}
+__global__ void __launch_bounds__(GWT) k_gram_fwd_fn(GramArgs a) {
+    using A = GramF32;
+    constexpr int NCH = GCN, NRING = 2;
+#include "gram_fwd_body.h"
 }
 
 // backward.  Staging: thread (w, l) loads tensors 8 (w & 3) + k (k = 0..7), channel quad
@@ -663,165 +627,8 @@ __global__ void __launch_bounds__(HWT) k_gram_bwd_h(GramArgs a) {
     }
 }
 
-// ---- fp32 mode (precision 0): the same staging and data movement on fp32 MFMA ----
-// forward: image [c][u][t] fp32 (row stride FRF floats: 80 B, conflict-free 16-B reads); the
-// symmetric Gram as three v_mfma_f32_16x16x4f32 tiles (U0 U0, U0 U1, U1 U1; U = 16 tensors) per
-// k-step, the fourth written as the mirror of (U0, U1): 3/4 of the MFMA cycles of one 32x32 tile.
-constexpr int FRF = 20;
-
-__global__ void __launch_bounds__(GWT) k_gram_fwd_f(GramArgs a) {
-    __shared__ __attribute__((aligned(16))) float I[GCS * 32 * FRF];   // [c][u][t]
-    int b, ch, c0;
-    decode(a, b, ch, c0);
-    const int tlen = a.T / a.nchunk, tbeg = ch * tlen;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i16 = lane & 15, kq = lane >> 4;
-    const int su = 8 * (w & 3) + (lane & 7), sq = lane >> 3, tb = w >> 2;
-    const bool real = su < a.nu;
-    const float* src = real ? (const float*)a.act + (size_t)a.uid[su] * a.tstride +
-                              (size_t)b * a.T * C + c0 + 4 * sq + (size_t)8 * tb * C
-                            : (const float*)a.zero16;
-    const size_t rs = real ? C : 0;
-    f32x4 acc[4][3];   // per channel: Gram tiles (U0, U0), (U0, U1), (U1, U1); (U1, U0) = mirror
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) acc[cc][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float4 v0[8], v1[8];
-    // unconditional loads (past the chunk: its last stage again), as k_gram_fwd_s
-    auto load = [&](float4 (&v)[8], int t0) {
-        const int tr = min(t0, tbeg + tlen - GSS);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = *reinterpret_cast<const float4*>(src + (size_t)(tr + k) * rs);
-    };
-    auto stage = [&](float4 (&v)[8], int t0) {
-        float4 f[4][2];   // channel 4 sq + j: rows 8 tb .. + 8
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            auto e = [&](int k) { return j == 0 ? v[k].x : j == 1 ? v[k].y : j == 2 ? v[k].z : v[k].w; };
-            f[j][0] = make_float4(e(0), e(1), e(2), e(3));
-            f[j][1] = make_float4(e(4), e(5), e(6), e(7));
-        }
-        load(v, t0 + 2 * GSS);
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float* row = &I[((4 * sq + j) * 32 + su) * FRF + 8 * tb];
-            *reinterpret_cast<float4*>(row) = f[j][0];
-            *reinterpret_cast<float4*>(row + 4) = f[j][1];
-        }
-        __syncthreads();
-        // 16x16x4 tiles: lane (i16, kq) supplies tensor U + i16 at rows 4 kq .. 4 kq + 3 (k-step s
-        // takes row 4 kq + s: any common permutation of K is the same Gram) for A and B alike
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-            const float* base = &I[(4 * w + cc) * 32 * FRF + 4 * kq];
-            const float4 u0 = *reinterpret_cast<const float4*>(base + i16 * FRF);
-            const float4 u1 = *reinterpret_cast<const float4*>(base + (16 + i16) * FRF);
-            const float a0[4] = {u0.x, u0.y, u0.z, u0.w}, a1[4] = {u1.x, u1.y, u1.z, u1.w};
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                acc[cc][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[st], a0[st], acc[cc][0], 0, 0, 0);
-                acc[cc][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[st], a1[st], acc[cc][1], 0, 0, 0);
-                acc[cc][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[st], a1[st], acc[cc][2], 0, 0, 0);
-            }
-        }
-    };
-    load(v0, tbeg);
-    load(v1, tbeg + GSS);
-    for (int t0 = tbeg; t0 < tbeg + tlen; t0 += 2 * GSS) {
-        stage(v0, t0);
-        stage(v1, t0 + GSS);
-    }
-#pragma unroll
-    for (int cc = 0; cc < 4; ++cc) {   // lane holds G[U + 4 kq + i][U' + i16] (C/D map of 16x16x4)
-        float* dst = a.gpart + (((size_t)b * a.nchunk + ch) * C + c0 + 4 * w + cc) * 1024;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rr = 4 * kq + i;
-            dst[rr * 32 + i16] = acc[cc][0][i];
-            dst[rr * 32 + 16 + i16] = acc[cc][1][i];
-            dst[(16 + i16) * 32 + rr] = acc[cc][1][i];
-            dst[(16 + rr) * 32 + 16 + i16] = acc[cc][2][i];
-        }
-    }
-}
-
-// fp32 forward for very few clips: k_gram_fwd_n's staging (8 channels, 64-row fills, wave w
-// = channel c0 + w) with k_gram_fwd_f's per-channel MFMA sequence, stage by stage: the same
-// partials bit for bit
-__global__ void __launch_bounds__(GWT) k_gram_fwd_fn(GramArgs a) {
-    __shared__ __attribute__((aligned(16))) float I[(GFN / GSS) * GCN * 32 * FRF];   // [stage][c][u][t]
-    constexpr int ncg = C / GCN;
-    const int nwg = a.B * a.nchunk * ncg;
-    int work = xcd_remap(blockIdx.x, nwg);
-    const int cgi = work % ncg; work /= ncg;
-    const int ch = work % a.nchunk, b = work / a.nchunk, c0 = cgi * GCN;
-    const int tlen = a.T / a.nchunk, tbeg = ch * tlen, tend = tbeg + tlen;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int i16 = lane & 15, kq = lane >> 4;
-    const int su = 8 * (w & 3) + (lane & 7), sq = (lane >> 3) & 1, g = (lane >> 4) + 4 * (w >> 2);
-    const bool real = su < a.nu;
-    const float* src = real ? (const float*)a.act + (size_t)a.uid[su] * a.tstride +
-                              (size_t)b * a.T * C + c0 + 4 * sq + (size_t)8 * g * C
-                            : (const float*)a.zero16;
-    const size_t rs = real ? C : 0;
-    f32x4 acc[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float4 v[2][8];
-    auto load = [&](float4 (&vv)[8], int t0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) vv[k] = *reinterpret_cast<const float4*>(src + (size_t)(t0 + k) * rs);
-    };
-    auto fill = [&](float4 (&vv)[8], int t0) {
-        float4 f[4][2];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            auto e = [&](int k) { return j == 0 ? vv[k].x : j == 1 ? vv[k].y : j == 2 ? vv[k].z : vv[k].w; };
-            f[j][0] = make_float4(e(0), e(1), e(2), e(3));
-            f[j][1] = make_float4(e(4), e(5), e(6), e(7));
-        }
-        if (t0 + 2 * GFN < tend) load(vv, t0 + 2 * GFN);
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float* row = &I[(((g >> 1) * GCN + 4 * sq + j) * 32 + su) * FRF + 8 * (g & 1)];
-            *reinterpret_cast<float4*>(row) = f[j][0];
-            *reinterpret_cast<float4*>(row + 4) = f[j][1];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int sg = 0; sg < GFN / GSS; ++sg) {
-            const float* base = &I[(sg * GCN + w) * 32 * FRF + 4 * kq];
-            const float4 u0 = *reinterpret_cast<const float4*>(base + i16 * FRF);
-            const float4 u1 = *reinterpret_cast<const float4*>(base + (16 + i16) * FRF);
-            const float a0[4] = {u0.x, u0.y, u0.z, u0.w}, a1[4] = {u1.x, u1.y, u1.z, u1.w};
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[st], a0[st], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[st], a1[st], acc[1], 0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[st], a1[st], acc[2], 0, 0, 0);
-            }
-        }
-    };
-    load(v[0], tbeg);
-    if (tbeg + GFN < tend) load(v[1], tbeg + GFN);
-    for (int t0 = tbeg; t0 < tend; t0 += 2 * GFN) {
-        fill(v[0], t0);
-        if (t0 + GFN < tend) fill(v[1], t0 + GFN);
-    }
-    float* dst = a.gpart + (((size_t)b * a.nchunk + ch) * C + c0 + w) * 1024;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int rr = 4 * kq + i;
-        dst[rr * 32 + i16] = acc[0][i];
-        dst[rr * 32 + 16 + i16] = acc[1][i];
-        dst[(16 + i16) * 32 + rr] = acc[1][i];
-        dst[(16 + rr) * 32 + 16 + i16] = acc[2][i];
-    }
-}
-
+// ---- fp32 mode (precision 0): the same staging and data movement on fp32 MFMA (forward: GramF32
+// in the forward body above) ----
 // backward: image [c][t][u] fp32, 32 floats per row with the four 8-tensor blocks swizzled
 // (block kq of row t at 8 (kq ^ (t & 3)): conflict-free 16-B reads); D_c = S~_c E_c on
 // v_mfma_f32_16x16x4f32: A = S~_c[u = 16 m + i16][u' = 8 kq + ks] in registers, B: lane

@@ -278,6 +278,51 @@ def test_few_clip_gram_kernels_bit_identical(precision, dev):
     e1.close()
 
 
+_GEO = {}
+
+
+def _geo_case(T, k, weights):
+    """16 clips of T samples and the oracle's embeds of clip k (computed once per T)."""
+    if T not in _GEO:
+        kw = CASES['ours']
+        xs = O.mu_law_numpy(synthetic_clips(16, T, 1000))
+        ext, _ = O.encoder_forward(xs[k], weights, O.needed_blocks(kw['cont_ids'], kw['style_ids']),
+                                   need_bottleneck=False)
+        _GEO[T] = (xs, O.content_embeds(ext, kw['cont_ids'], kw['cnt_channels']),
+                   O.style_embeds(ext, kw['style_ids'], kw['gatys'], kw['nb_channels']))
+    return _GEO[T]
+
+
+@pytest.mark.parametrize('T', [512, 1024, 1536])
+@pytest.mark.parametrize('precision', ['split', 'fp32'])
+def test_gram_fwd_geometries_bit_identical_small(precision, T, weights, dev):
+    """The ours-Gram forward's one body (gram_fwd_body.h) in its three geometries: the same clip
+    alone (B = 1: k_gram_fwd_n<3, 4> / k_gram_fwd_fn), in a 2-clip context (k_gram_fwd_n<2, 8> /
+    k_gram_fwd_fn) and as clip 11 of a 16-clip context (64 workgroups of 32 channels:
+    k_gram_fwd_s<3> / k_gram_fwd_f) gives the same style embeds bit for bit, and the B = 1 result
+    meets the oracle bars of test_split_embeds_match_oracle / test_gpu_parity's
+    test_embeds_match_oracle.  One chunk of 32 / 64 / 96 stages = 8 / 16 / 24 narrow fills: the
+    ring remainders 2, 1, 0 of a 3-deep ring and 0 of a 2-deep one."""
+    k = 11
+    kw = CASES['ours']
+    xs, ref_c, ref_s = _geo_case(T, k, weights)
+    x16 = torch.tensor(xs, dtype=torch.float32, device=dev)
+    got = {}
+    for B, idx in ((1, [k]), (2, [3, k]), (16, list(range(16)))):
+        eng = _engine(B, T, kw, weights, precision)
+        emb_c, emb_s = eng.embeds(x16[idx].contiguous())
+        got[B] = (emb_c[idx.index(k)].clone(), emb_s[idx.index(k)].clone())
+        torch.cuda.synchronize()
+        eng.close()
+    ec, es = rel(got[1][0].cpu().numpy(), ref_c), rel(got[1][1].cpu().numpy(), ref_s)
+    print('%s T=%d embeds rel-L2: content %.3g style %.3g' % (precision, T, ec, es))
+    for B in (2, 16):
+        assert torch.equal(got[B][1], got[1][1]), ('style embeds differ from B = 1 at B = %d' % B)
+        assert torch.equal(got[B][0], got[1][0]), B
+    assert ec <= 1e-5
+    assert es <= (1e-4 if precision == 'split' else 1e-5)
+
+
 def test_graph_replays_bitwise_at_bench_length(dev):
     """Every replay of a captured ast_loss_grad equals the eager call bit for bit, at the bench's
     clip length with 8 clips (one per XCD in the block kernels' tile order), with eager work

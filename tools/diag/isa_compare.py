@@ -1,11 +1,12 @@
-"""Compare the compiled split block kernels of two source trees, kernel by kernel: the instruction
-text (comments, directives and debug lines stripped; the function index of local labels
-normalised) and the kernel descriptor values (register, spill, LDS and scratch sizes).  For
-refactors that must not change what runs on the GPU.  Kernels are matched by base name plus
-their bool template arguments; every split block source (block_*_split*.hip) of each tree is
-compiled with the project's flags (_build.FLAGS + EXTRA, --cuda-device-only -S).
+"""Compare the compiled kernels of two source trees, kernel by kernel: the instruction text
+(comments, directives and debug lines stripped; the function index of local labels normalised)
+and the kernel descriptor values (register, spill, LDS and scratch sizes).  For refactors that
+must not change what runs on the GPU.  Kernels are matched by base name plus all their template
+arguments; every selected source of each tree (--sources, a glob within csrc; default the split
+block sources block_*_split*.hip) is compiled with the project's flags for that source
+(_build.FLAGS + EXTRA.get(name, []), --cuda-device-only -S).
 
-usage: python tools/diag/isa_compare.py <old csrc dir> <new csrc dir> [--keep DIR]
+usage: python tools/diag/isa_compare.py <old csrc dir> <new csrc dir> [--sources GLOB] [--keep DIR]
 --keep DIR leaves the listings in DIR/old and DIR/new; a directory of such listings may stand in
 for a csrc directory.  Exit status 0 when every kernel compares equal"""
 import difflib
@@ -22,17 +23,18 @@ from audio_style_transfer_amd import _build  # noqa: E402
 
 DESC = ('.vgpr_count', '.agpr_count', '.sgpr_count', '.sgpr_spill_count', '.vgpr_spill_count',
         '.group_segment_fixed_size', '.private_segment_fixed_size')
-CW = _build.EXTRA['block_fwd_split.hip']
+SOURCES = 'block_*_split*.hip'
 
 
-def compile_tree(csrc, out):
-    srcs = sorted(glob.glob(os.path.join(csrc, 'block_*_split*.hip')))
+def compile_tree(csrc, out, sources=SOURCES):
+    srcs = sorted(glob.glob(os.path.join(csrc, sources)))
     if not srcs:   # a directory of listings kept from an earlier run
-        return sorted(glob.glob(os.path.join(csrc, 'block_*_split*.s')))
+        return sorted(glob.glob(os.path.join(csrc, os.path.splitext(sources)[0] + '.s')))
 
     def cc(src):
         s = os.path.join(out, os.path.basename(src)[:-4] + '.s')
-        cmd = [_build.HIPCC, *_build.FLAGS, '-I', csrc, *CW, '--cuda-device-only', '-S', src, '-o', s]
+        cmd = [_build.HIPCC, *_build.FLAGS, '-I', csrc, *_build.EXTRA.get(os.path.basename(src), []),
+               '--cuda-device-only', '-S', src, '-o', s]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError('hipcc failed for %s:\n%s' % (src, r.stderr))
@@ -48,10 +50,10 @@ def demangle(names):
 
 
 def key_of(demangled):
-    """'k_block_fwd_s16<true,false,false>' from any spelling of the kernel's name"""
+    """'k_block_fwd_s16<true,false,false>' / 'k_gram_fwd_n<2,4>' from the kernel's demangled name"""
     m = re.search(r'(\w+)(?:<(.*?)>)?\(', demangled)
-    args = re.findall(r'\b(true|false)\b', m.group(2) or '')
-    return m.group(1) + ('<%s>' % ','.join(args) if args else '')
+    args = re.sub(r'\s+', '', m.group(2) or '')
+    return m.group(1) + ('<%s>' % args if args else '')
 
 
 def kernels(path):
@@ -99,6 +101,7 @@ def tree_kernels(listings):
 
 def main():
     keep = sys.argv[sys.argv.index('--keep') + 1] if '--keep' in sys.argv else None
+    sources = sys.argv[sys.argv.index('--sources') + 1] if '--sources' in sys.argv else SOURCES
     old_dir, new_dir = sys.argv[1], sys.argv[2]
     with tempfile.TemporaryDirectory() as tmp:
         root = keep or tmp
@@ -106,7 +109,7 @@ def main():
         for tag, d in (('old', old_dir), ('new', new_dir)):
             out = os.path.join(root, tag)
             os.makedirs(out, exist_ok=True)
-            trees.append(tree_kernels(compile_tree(d, out)))
+            trees.append(tree_kernels(compile_tree(d, out, sources)))
     old, new = trees
     bad = 0
     for k in sorted(set(old) | set(new)):
