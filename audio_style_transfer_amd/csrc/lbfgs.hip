@@ -16,6 +16,16 @@
 //   * after an accepted step (NEW_X): iteration count against maxiter first, then
 //     ||g||_inf <= pgtol, then (f_old - f) <= factr*eps * max(|f_old|, |f|, 1); then the pair
 //     update, skipped when s'y <= eps * (-g_old'd * stp).
+// Two rules are scipy.optimize.minimize's own and not the Fortran's, and both are kept, so that
+// iterations, evaluations and the loss history are those of the scipy path:
+//   * iterations (info[1]) are scipy's nit: accepted points only.  An abnormal end of the line
+//     search adds none (the Fortran's iter counts that one too);
+//   * a trial point that is bit-identical, as a whole fp64 array, to the previous trial (the
+//     search falls back to stp = stx when stx is the point just evaluated, at the fp32 noise
+//     floor) is not handed back: scipy's wrapper serves it from its cache without calling the
+//     function.  The loss is deterministic, so f and g are the ones at hand, and the search is
+//     re-entered at once with them; ifun advances and the maxls test applies, the evaluation
+//     count (info[2]) and the history do not move.
 // f and g come from ast_loss_grad in fp32 and are widened to fp64, as the ScipyOptimizerInterface
 // does; x is kept in fp64 and handed to the loss as fp32 (the TF variable's dtype).
 //
@@ -379,26 +389,34 @@ __global__ void __launch_bounds__(NT) k_lbfgs_step(StepArgs a) {
         double gd = 0.0;
         for (int i = threadIdx.x; i < T; i += NT) gd += (double)g[i] * w.D[i];
         gd = block_sum(gd, red);
-        if (dcsrch_iter(s, f, gd)) {                             // FG: another trial
+        // FG: another trial, until one is a new point (a trial bit-identical to the previous
+        // one is scipy's cache hit: same f, same gd, no evaluation)
+        bool accept = false;
+        for (;;) {
+            if (!dcsrch_iter(s, f, gd)) { accept = true; break; }
             s.ifun++;
             if (s.ifun - 1 >= s.maxls) {                         // iback >= maxls: give up
                 __syncthreads();
                 put_x(xd, w.X[s.xi], T);                         // restore the base point
-                if (s.col == 0) { s.phase = 0; s.reason = LB_ABNORMAL; s.iter++; }
+                if (s.col == 0) { s.phase = 0; s.reason = LB_ABNORMAL; }
                 else {
                     s.col = 0; s.head = 0; s.theta = 1.0;
                     if (new_direction(s, w, xd, T, red, alpha)) { s.phase = 0; s.reason = LB_ABNORMAL; }
                 }
-            } else {
-                const double* t = w.X[s.xi];
-                double* trial = w.X[1 - s.xi];
-                for (int i = threadIdx.x; i < T; i += NT) {
-                    const double v = mul_add_rn(s.stp, w.D[i], t[i]);
-                    trial[i] = v;
-                    xd[i] = (float)v;
-                }
+                break;
             }
-        } else {                                                 // NEW_X
+            const double* t = w.X[s.xi];
+            double* trial = w.X[1 - s.xi];
+            double moved = 0.0;
+            for (int i = threadIdx.x; i < T; i += NT) {
+                const double v = mul_add_rn(s.stp, w.D[i], t[i]);   // stp == 1: z again, bit for bit
+                if (v != trial[i]) moved = 1.0;
+                trial[i] = v;
+                xd[i] = (float)v;
+            }
+            if (block_max(moved, red) != 0.0) break;
+        }
+        if (accept) {                                            // NEW_X
             s.iter++;
             const double stp = s.stp;
             double gmax = 0.0, rr = 0.0;

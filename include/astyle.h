@@ -338,7 +338,12 @@ int ast_adam_step_dev(ast_ctx* ctx, float* x_dev, float* m_dev, float* v_dev, co
  * active_dev [batch] int (NULL = all) selects the clips that run.  info_dev [batch, 4] =
  * (phase, iterations, evaluations, reason: 0 running, 1 maxiter, 2 pgtol, 3 rel. reduction
  * of f, 4 abnormal line search, 5 the workspace header is not one begin wrote for this batch
- * and T); x64_dev [batch, T] (may be NULL) the current float64 point.  step / state / a
+ * and T); x64_dev [batch, T] (may be NULL) the current float64 point.  Both counts are
+ * scipy.optimize.minimize's: iterations are its nit, accepted points only (an abnormal end of
+ * the line search adds none); evaluations are its nfev, so a trial point bit-identical (the
+ * whole float64 array) to the previous trial is not handed back for evaluation, as scipy
+ * serves it from its cache -- the search goes on inside the same step with the f and grad at
+ * hand, and neither the count nor the history (ast_lbfgs_history) moves.  step / state / a
  * continuation on a workspace this context never started with x0 fail with AST_E_STATE.
  * begin/step allocate nothing, so the step pair is hipGraph-capturable. */
 int ast_lbfgs_workspace_bytes(ast_ctx* ctx, int m, size_t* out_bytes);
