@@ -22,7 +22,7 @@ import numpy as np
 from . import astyle_oracle as O
 
 
-def forward(x, W, n_blocks=30, me=None, mu=None, dtype=np.float64):
+def forward(x, W, n_blocks=30, me=None, mu=None, dtype=np.float64, need_bottleneck=False):
     """encoder_forward with optional forced relu masks; returns extracts, cache, (me, mu)."""
     x = np.asarray(x, dtype=dtype)
     e = O.conv1d_same((x / 128.0)[:, None], W['ae_startconv/W'].astype(dtype),
@@ -44,6 +44,9 @@ def forward(x, W, n_blocks=30, me=None, mu=None, dtype=np.float64):
         mu_out.append(m_u)
     if n_blocks == O.N_BLOCKS:
         ext.append(e)
+        if need_bottleneck:    # (linear in e_30: no relu decision of its own)
+            ext.append(O.conv1d_same(e, W['ae_bottleneck/W'].astype(dtype),
+                                     W['ae_bottleneck/biases'].astype(dtype), 1))
     return ext, {'es': es, 'us': us, 'n_blocks': n_blocks}, (me_out, mu_out)
 
 
@@ -52,6 +55,8 @@ def backward(cache, masks, W, ext_grads, dtype=np.float64):
     me, mu = masks
     T = es[0].shape[0]
     g = np.zeros((T, O.C), dtype=dtype)
+    if 31 in ext_grads:
+        g += O.conv1d_same_bwd(ext_grads[31], W['ae_bottleneck/W'].astype(dtype), 1)
     if 30 in ext_grads:
         g += ext_grads[30]
     for l in reversed(range(n_blocks)):
@@ -66,12 +71,12 @@ def backward(cache, masks, W, ext_grads, dtype=np.float64):
 
 
 def loss_and_grad(x, W, *, cont_ids, style_ids, phi_c, phi_s, lambd=100.0, me=None, mu=None,
-                  nb_channels=128, cnt_channels=128, dtype=np.float64):
-    """O.loss_and_grad (ours Gram, gamma = 0, no bottleneck tap) on forced masks."""
+                  nb_channels=128, cnt_channels=128, gatys=False, dtype=np.float64):
+    """O.loss_and_grad (gamma = 0) on forced masks."""
     nb = O.needed_blocks(cont_ids, style_ids)
-    ext, cache, masks = forward(x, W, nb, me, mu, dtype)
+    ext, cache, masks = forward(x, W, nb, me, mu, dtype, need_bottleneck=31 in cont_ids)
     content, style, grads = O.tap_terms(ext, cont_ids=cont_ids, style_ids=style_ids,
-                                        phi_c=phi_c, phi_s=phi_s, lambd=lambd,
+                                        phi_c=phi_c, phi_s=phi_s, lambd=lambd, gatys=gatys,
                                         nb_channels=nb_channels, cnt_channels=cnt_channels)
     g = backward(cache, masks, W, grads, dtype)
     return np.array([content + lambd * style, content, style, 0.0]), g, ext, masks
