@@ -14,6 +14,7 @@
 #include "../../include/astyle.h"
 #include "common.h"
 #include "ckpt.h"
+#include "pack.h"
 
 using namespace ast;
 
@@ -50,43 +51,9 @@ constexpr size_t WD = 0, WDT = 3 * C * C, BD = 6 * C * C, WR = BD + C, WRT = WR 
 constexpr size_t WB_OFF = BLK_OFF + NBLK_MAX * BLK_SZ;   // [128][16]
 constexpr size_t BB_OFF = WB_OFF + C * 16;
 constexpr size_t W_TOTAL = BB_OFF + 16;
-// bf16 MFMA fragments (precision 1), u16 elements per block.
-// MFMA A-fragment order for block_fwd_bf16.hip: WFB [3 taps][4 q][8 kb][64 lanes][8],
-// lane (m, h) element e = W_d[tap][ci = 16 kb + 8 h + e][co = 32 q + m];
-// WRFB [4 q2][8 s][64][8], element e = W_r[co = kperm(s, h, e)][co2 = 32 q2 + m].
-// block_bwd_bf16.hip: WBFB [3][4 q][8 kb][64][8], element e = W_d[tap][32 q + m][16 kb + 8 h + e];
-// WRBFB [4 q][8 kb][64][8], element e = W_r[32 q + m][16 kb + 8 h + e]
-constexpr size_t WFB = 0, WRFB = 3 * C * C, WBFB = 4 * C * C, WRBFB = 7 * C * C, BLKB_SZ = 8 * C * C;
-inline int kperm(int s, int h, int e) { return 32 * (s >> 1) + 16 * (s & 1) + (e & 3) + 8 * (e >> 2) + 4 * h; }
-// split-fp16 fragments (precision 2), uint4 (8 fp16) units per block: WDF [4][3][8][2][64],
-// WRF [4][8][2][64], WRB [4][8][2][64], WDB [4][3][8][2][64] (common.h, FwdArgsS / BwdArgsS)
-constexpr size_t SWDF = 0, SWRF = 4 * 3 * 8 * 2 * 64, SWRB = SWRF + 4 * 8 * 2 * 64,
-                 SWDB = SWRB + 4 * 8 * 2 * 64, SBLK = SWDB + 4 * 3 * 8 * 2 * 64;
-
-// power-of-two exponent k that puts max |w| in [2^13, 2^14) (fp16 range, splitwave.h)
-int weight_exp(const float* w, size_t n) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
-    int e = 0;
-    (void)std::frexp(mx, &e);
-    return 14 - e;
-}
-// fp16 halves of w 2^k (round to nearest): hi, lo = fp16(w 2^k - hi)
-void split_half(float w, int k, uint16_t& hi, uint16_t& lo) {
-    const float v = std::ldexp(w, k);
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)(v - (float)h);
-    memcpy(&hi, &h, 2);
-    memcpy(&lo, &l, 2);
-}
-
-uint16_t host_bf16(float f) {   // round to nearest even
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
+// the bf16 (precision 1) and split-fp16 (precision 2) MFMA fragments of the block weights, their
+// offsets per block (WFB .. BLKB_SZ, SWDF .. SBLK) and their packing: pack.h
+static_assert(WC == C, "pack.h packs C x C weights");
 
 struct Occ { int ext, tensor, off, ncol; };
 
@@ -241,16 +208,14 @@ int plan(const ast_cfg* c, ast_ctx* x) {
     if (c->gatys) {
         // target rows per Gatys chunk (ASTYLE_GATYS_ROWS for A/B): 8192 measured 0.2-0.4 ms / step
         // faster than 4096 (half the [C][C] partials through k_style_gatys), 16384 the same as 8192
-        static int grows = -1;
-        if (grows < 0) { const char* e = getenv("ASTYLE_GATYS_ROWS"); grows = e ? std::max(512, atoi(e)) : 8192; }
+        static const int grows = (int)std::max(512L, env_int("ASTYLE_GATYS_ROWS", 8192, INT_MIN, INT_MAX));
         nch = gram_chunks(c->T, 64, grows);    // whole 64-row stages (bf16 / split; fp32: 32)
         x->gpart_elems = (size_t)c->batch * nch * x->nu * C * C;
         x->smat_elems = (size_t)c->batch * x->nu * C * C;
     } else {
         // target rows per chunk (ASTYLE_GRAM_ROWS for A/B): 4096 measured 0.6 ms / step faster than 1024
         // in the Gram forward and 0.25 ms in k_style_ours (a quarter of the partials), 8192 the same
-        static int rows = -1;
-        if (rows < 0) { const char* e = getenv("ASTYLE_GRAM_ROWS"); rows = e ? std::max(512, atoi(e)) : 4096; }
+        static const int rows = (int)std::max(512L, env_int("ASTYLE_GRAM_ROWS", 4096, INT_MIN, INT_MAX));
         nch = gram_chunks(c->T, 32, rows);     // whole 2 x 16-row split / fp32 stages (bf16: 16)
         x->gpart_elems = (size_t)c->batch * nch * C * 1024;
         x->smat_elems = (size_t)c->batch * C * 1024;
@@ -280,14 +245,8 @@ int plan(const ast_cfg* c, ast_ctx* x) {
 // default 1 MiB + 4 KiB): at B = 256, T = 16384 a tensor is exactly 2^31 bytes, so without a pad
 // the Gram kernels' 30 concurrent streams start at the same offset modulo every power of two
 // (measured: Gram forward 13.2 -> 11.1-11.4 ms with the pad).
-static size_t tensor_pad() {
-    static long pad = -1;
-    if (pad < 0) {
-        const char* e = getenv("ASTYLE_TPAD");
-        pad = e ? atol(e) : 263168;
-        if (pad < 0) pad = 0;
-        pad = (pad + 127) / 128 * 128;   // whole 512-B rows
-    }
+static size_t tensor_pad() {   // (whole 512-B rows)
+    static const long pad = (std::max(0L, env_int("ASTYLE_TPAD", 263168)) + 127) / 128 * 128;
     return (size_t)pad;
 }
 
@@ -299,70 +258,90 @@ static size_t tensor_pad() {
 // ran 26.8-27.1 ms in 19 of 22 (the DRAM credit stalls of the write-over-read pattern); in round 5
 // one box of five ran every in-place Gram backward at 27.1-27.3 ms; on fast boxes the two modes are
 // within +-0.4 ms (round 5 and 6 A/Bs).  ASTYLE_DOOP=1 / 0 forces either mode (A/B runs).
-static int doop_env() {
-    static int v = -2;
-    if (v == -2) { const char* e = getenv("ASTYLE_DOOP"); v = e ? (atoi(e) != 0) : -1; }
-    return v;
-}
+static int doop_env() { static const int v = env_flag("ASTYLE_DOOP", -1); return v; }   // -1: not forced
 // Byte offset of the D buffer inside its allocation (ASTYLE_DPAD, A/B of the Gram backward's
 // read / write address interplay; a multiple of 256)
-static size_t d_pad() {
-    static long v = -1;
-    if (v < 0) { const char* e = getenv("ASTYLE_DPAD"); v = e ? (std::max(0L, atol(e)) / 256) * 256 : 0; }
-    return (size_t)v;
-}
+static size_t d_pad() { static const long v = std::max(0L, env_int("ASTYLE_DPAD", 0)) / 256 * 256; return (size_t)v; }
 
 int fused_content_occ(const ast_ctx* x);
 
 // ASTYLE_MFMA16: the split block kernels on v_mfma_f32_16x16x32_f16 (k_block_fwd_s16 /
 // k_block_bwd_s16; round 6: measured): 0 = neither, 1 = forward and backward, 2 = the backward only (default:
 // backward -0.3..-1.2 %, forward +4 % on 16x16x32), 3 = the forward only; read once per process, since the weight fragments are packed for the kernels that will read them
-static int mfma16_mode() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ASTYLE_MFMA16"); v = e ? atoi(e) : 2; if (v < 0 || v > 3) v = 2; }
-    return v;
-}
+static int mfma16_mode() { static const int v = (int)env_int("ASTYLE_MFMA16", 2, 0, 3); return v; }
 static bool mfma16_fwd() { const int m = mfma16_mode(); return m == 1 || m == 3; }
 static bool mfma16_bwd() { const int m = mfma16_mode(); return m == 1 || m == 2; }
-// (K index kk, output-channel index mm) of element e of lane ln in fragment slot kb of wave w, in
-// the 32x32x16 or (m16) the 16x16x32 layout (common.h: the split weight layouts)
-static void frag_index(bool m16, int kb, int ln, int e, int w, int& kk, int& mm) {
-    if (m16) {
-        const int ii = ln & 15, qq = ln >> 4;
-        kk = 32 * (kb >> 1) + 8 * qq + e;
-        mm = 32 * w + 16 * (kb & 1) + ii;
-    } else {
-        kk = 16 * kb + 8 * (ln >> 5) + e;
-        mm = 32 * w + (ln & 31);
+
+// Every device buffer of a context, in the order ast_create allocates them (the guard test and
+// the address-dependent Gram timings were measured with this order): ast_create walks the table,
+// ast_workspace_bytes is the sum of its byte counts.  Needs plan() and decide_doop() done on x.
+struct Buf {
+    const char* name;                        // as ast_debug_check_guards reports it
+    size_t bytes;
+    bool zero;                               // cleared at create
+    void (*set)(ast_ctx*, void*, int);       // assigns the destination field
+    int t;                                   //   (its index, for per-tensor buffers)
+};
+std::vector<Buf> buffer_table(const ast_cfg& c, const ast_ctx* x) {
+    std::vector<Buf> tab;
+#define BUF_AT(dst, idx, bytes, zero) tab.push_back({#dst, (size_t)(bytes), zero, [](ast_ctx* x, void* p, int t) { (void)t; dst = (decltype(dst))p; }, idx})
+#define BUF(dst, bytes, zero) BUF_AT(dst, 0, bytes, zero)
+    const size_t BT = (size_t)c.batch * c.T, BTC = BT * C;
+    const size_t es = c.precision == 1 ? 2 : 4;                       // bytes per stored element
+    const size_t acts = (size_t)(x->nblk + 1) * (BTC + tensor_pad()) * es;
+    if (c.precision == 2) {
+        BUF(x->wtss, (size_t)NBLK_MAX * SBLK * 16, true);
+        BUF(x->gmax_e, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4, false);
+        BUF(x->gmax_g, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4, false);
     }
+    BUF(x->wts, W_TOTAL * 4, true);
+    BUF(x->wtsb, (size_t)NBLK_MAX * BLKB_SZ * 2, true);
+    BUF(x->act, acts, false);
+    if (x->doop) BUF(x->dgrad, acts + d_pad(), false);   // (the walker moves the pointer up by d_pad())
+    BUF(x->mu, (size_t)x->nblk * BT * 16, false);
+    BUF(x->me, (size_t)x->nblk * BT * 16, false);
+    BUF(x->chain[0], BTC * es, false);
+    BUF(x->chain[1], BTC * es, false);
+    // a content-gradient buffer per tensor with a direct content tap (unless the Gram backward
+    // adds that tap's gradient itself), and for tensor 30 under a bottleneck tap or the encoding
+    const int fuse_u = fused_content_occ(x);
+    for (int t = 0; t <= NBLK_MAX; ++t)
+        if ((x->tensor_has_direct_content[t] && !(fuse_u >= 0 && x->uid[fuse_u] == t)) || (t == 30 && (x->need_bott || c.with_encoding)))
+            BUF_AT(x->cg_buf[t], t, BTC * es, false);
+    if (x->need_bott) {
+        BUF(x->bott, BT * 16 * 4, false);
+        BUF(x->gbott, BT * 16 * 4, false);
+    }
+    BUF(x->gpart, x->gpart_elems * 4, false);
+    BUF(x->smat, x->smat_elems * 4, false);
+    if (c.gatys && c.precision == 1) BUF(x->smatb, x->smat_elems * 2, false);
+    BUF(x->zero, 256, true);
+    BUF(x->rflags, (size_t)c.batch * 4, true);
+    BUF(x->rflags_last, (size_t)c.batch * 4, true);
+    BUF(x->spart, (size_t)c.batch * C * 4, false);
+    BUF(x->cpart, (size_t)c.batch * x->occ.size() * (c.T / CROWS) * 4, false);
+    if (const int nf = stft_frames(c.T)) {   // STFT regulariser
+        BUF(x->stft_tw, 1024 * 8, false);
+        BUF(x->stft_fpart, (size_t)c.batch * nf * 4, false);
+        BUF(x->stft_gfr, (size_t)c.batch * nf * 1024 * 4, false);
+    }
+    BUF(x->anc_part, (size_t)c.batch * anchor_chunks(c.T) * 2 * 4, false);
+    BUF(x->anc_loss, (size_t)c.batch * 4, false);
+    if (c.with_encoding) {
+        const size_t BR = (size_t)c.batch * (c.T / 512);
+        BUF(x->enc, BR * 16 * 4, false);
+        BUF(x->enc_d, BR * 16 * 4, false);
+        BUF(x->enc_part, BR * 4, false);
+        BUF(x->enc_loss, (size_t)c.batch * 4, false);
+    }
+#undef BUF
+#undef BUF_AT
+    return tab;
 }
 
 size_t workspace_bytes(const ast_cfg* c, const ast_ctx* x) {
-    const size_t BTC = (size_t)c->batch * c->T * C;
-    const size_t es = c->precision == 1 ? 2 : 4;
     size_t n = 0;
-    n += W_TOTAL * 4 + (size_t)NBLK_MAX * BLKB_SZ * 2;
-    if (c->precision == 2) n += (size_t)NBLK_MAX * SBLK * 16 + 2 * (size_t)(NBLK_MAX + 1) * c->batch * GCLIP_W * 4;
-    n += (size_t)(x->nblk + 1) * (BTC + tensor_pad()) * es * (x->doop ? 2 : 1);   // act (+ D)
-    if (x->doop) n += d_pad();
-    n += 2 * (size_t)x->nblk * c->batch * c->T * 16;        // mu, me
-    n += 2 * BTC * es;                                      // chain
-    int ncg = 0;
-    const int fuse_u = fused_content_occ(x);   // (as ast_create: no content-gradient buffer for it)
-    for (int t = 0; t <= NBLK_MAX; ++t)
-        if ((x->tensor_has_direct_content[t] && !(fuse_u >= 0 && x->uid[fuse_u] == t)) || (t == 30 && (x->need_bott || c->with_encoding))) ++ncg;
-    n += (size_t)ncg * BTC * es;
-    if (x->need_bott) n += 2 * (size_t)c->batch * c->T * 16 * 4;
-    n += x->gpart_elems * 4;                                // gpart
-    n += x->smat_elems * (c->gatys && es == 2 ? 6 : 4);     // smat (+ bf16 copy)
-    n += (size_t)c->batch * C * 4;                          // spart
-    n += 256;                                               // zero line
-    n += (size_t)c->batch * 4;                              // range flags
-    n += (size_t)c->batch * x->occ.size() * (c->T / CROWS) * 4;
-    const int nf = stft_frames(c->T);
-    if (nf) n += 1024 * 8 + (size_t)c->batch * nf * (1 + 1024) * 4;   // STFT regulariser
-    n += (size_t)c->batch * (2 * anchor_chunks(c->T) + 1) * 4;        // seam anchor partials, values
-    if (c->with_encoding) n += (size_t)c->batch * ((size_t)(c->T / 512) * 33 + 1) * 4;   // enc, d, hop partials, values
+    for (const Buf& b : buffer_table(*c, x)) n += b.bytes;
     return n;
 }
 
@@ -379,10 +358,6 @@ static void decide_doop(const ast_cfg* c, ast_ctx* x) {
     const size_t margin = std::max<size_t>((size_t)16 << 30, tot / 10);
     x->doop = need + margin <= fr;
 }
-
-void launch_gram_bwd_any(ast_ctx* x, const GramArgs& g, hipStream_t s);
-GramArgs gram_args(ast_ctx* x);
-GatysArgs gatys_args(ast_ctx* x);
 
 // Where both placements fit (x->dgrad allocated, D at least 4 GiB) and ASTYLE_DOOP does not force
 // one, the first evaluation that is not being captured into a graph times its own Gram backward in
@@ -440,11 +415,7 @@ static int timed_gram_bwd(ast_ctx* x, F launch, hipStream_t s) {
 // sides; ast_debug_check_guards reports any band a kernel wrote into (out-of-bounds stores)
 constexpr size_t GUARD_BYTES = 64 << 10;
 constexpr int GUARD_FILL = 0x5a;
-static bool guard_on() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ASTYLE_GUARD"); v = e && atoi(e) ? 1 : 0; }
-    return v == 1;
-}
+static bool guard_on() { static const bool on = env_flag("ASTYLE_GUARD", 0) != 0; return on; }
 
 int dalloc(ast_ctx* x, void** p, size_t bytes, const char* name = "") {
     if (guard_on()) {
@@ -555,8 +526,7 @@ void launch_gram_bwd_any(ast_ctx* x, const GramArgs& g, hipStream_t s) {
 // is skipped.
 // ASTYLE_FUSE_CONTENT=0 keeps the separate kernel.
 int fused_content_occ(const ast_ctx* x) {
-    static int en = -1;
-    if (en < 0) { const char* e = getenv("ASTYLE_FUSE_CONTENT"); en = e ? (atoi(e) != 0) : 1; }
+    static const bool en = env_flag("ASTYLE_FUSE_CONTENT", 1) != 0;
     if (!en || x->cfg.precision != 2 || x->occ.size() != 1 || x->need_bott || x->cfg.with_encoding) return -1;
     const Occ& o = x->occ[0];
     if (o.ext == 31 || !x->tensor_in_style[o.tensor]) return -1;
@@ -574,17 +544,50 @@ void* cg_live(const ast_ctx* x, int t) {
 // the tensor the backward chain starts at: the highest with a loss gradient
 int bwd_top(const ast_ctx* x) { return x->enc_phi ? NBLK_MAX : x->top_tap; }
 
-GramArgs gram_args(ast_ctx* x) {
-    GramArgs g;
+// GramArgs and GatysArgs name what they share alike: the common prefix, the top tensor's max
+// inside the split backward, and its fused content tap
+template <class A>
+A gram_common_args(ast_ctx* x) {
+    A g;
     memset(&g, 0, sizeof(g));
     g.act = x->act; g.actw = x->dgrad ? x->dgrad : x->act; g.tstride = x->tstride;
     g.nu = x->nu;
     for (int u = 0; u < x->nu; ++u) { g.uid[u] = x->uid[u]; g.cg[u] = cg_live(x, x->uid[u]); }
-    g.gpart = x->gpart; g.smat = x->smat; g.zero16 = x->zero;
+    g.gpart = x->gpart; g.smat = x->smat;
     g.B = x->cfg.batch; g.T = x->cfg.T; g.nchunk = x->nchunk;
     g.top_u = -1; g.gmax_top = nullptr;
     g.cont_u = -1;
     return g;
+}
+GramArgs gram_args(ast_ctx* x) {
+    GramArgs g = gram_common_args<GramArgs>(x);
+    g.zero16 = x->zero;
+    return g;
+}
+GatysArgs gatys_args(ast_ctx* x) {
+    GatysArgs g = gram_common_args<GatysArgs>(x);
+    g.smatb = x->smatb;
+    return g;
+}
+// split, the top tensor style-tapped: the backward chain's first max |tot| inside the Gram backward
+template <class A>
+bool set_top_max(ast_ctx* x, A& g, int ntop, hipStream_t s) {
+    if (!x->split || !x->tensor_in_style[ntop]) return false;
+    for (int u = 0; u < x->nu; ++u) if (x->uid[u] == ntop) g.top_u = u;
+    g.gmax_top = x->gmax_g + (size_t)ntop * x->cfg.batch * GCLIP_W;
+    launch_zero32(x->gmax_g, (size_t)(NBLK_MAX + 1) * x->cfg.batch * GCLIP_W * 4, s, 2);
+    return g.top_u >= 0;
+}
+// the split Gram backward adds the content tap of unique tensor fuse_u (fused_content_occ) itself;
+// its squared errors go to cpart (ours: GRAM_CSLOT-row slots; Gatys: one slot per 512-row tile)
+template <class A>
+void set_fused_content(ast_ctx* x, A& g, int fuse_u, float ccoef) {
+    const Occ& o = x->occ[0];
+    g.cg[fuse_u] = nullptr;
+    g.cont_u = fuse_u;
+    g.cont_phi = x->phi_c; g.cont_phi_bstride = x->phi_c_shared ? 0 : (size_t)x->cfg.T * x->ncc;
+    g.cont_ncc = x->ncc; g.cont_off = o.off; g.cont_ncol = o.ncol; g.cont_coef = ccoef;
+    g.cont_part = x->cpart; g.cont_pstride = (size_t)x->ncpart;
 }
 
 StyleArgs style_args(ast_ctx* x) {
@@ -601,19 +604,6 @@ StyleArgs style_args(ast_ctx* x) {
     a.coef = x->cfg.lambd * 1e3f * 2.0f / (float)(a.nb * x->L * x->L);
     a.B = x->cfg.batch;
     return a;
-}
-
-GatysArgs gatys_args(ast_ctx* x) {
-    GatysArgs g;
-    memset(&g, 0, sizeof(g));
-    g.act = x->act; g.actw = x->dgrad ? x->dgrad : x->act; g.tstride = x->tstride;
-    g.nu = x->nu;
-    for (int u = 0; u < x->nu; ++u) { g.uid[u] = x->uid[u]; g.cg[u] = cg_live(x, x->uid[u]); }
-    g.gpart = x->gpart; g.smat = x->smat; g.smatb = x->smatb;
-    g.B = x->cfg.batch; g.T = x->cfg.T; g.nchunk = x->nchunk;
-    g.cont_u = -1;
-    g.top_u = -1; g.gmax_top = nullptr;
-    return g;
 }
 
 GatysStyleArgs gatys_style_args(ast_ctx* x) {
@@ -713,9 +703,11 @@ int ast_ot_admm(const double* p_mod, const double* p_ref, int nprob, int n1, int
     return 0;
 }
 
-// Diagnostic hook (not in astyle.h): device buffer of 12 u64 phase-cycle sums that
-// -DASTYLE_STAMPS builds of the bf16 block kernels accumulate into; NULL disables.
-int ast_debug_stamps(void* dev_u64x20x64) {   // 64 rows of 20: [0..15] sums, [16] / [17] max / min wave lifetime, [18] / [19] first start / last end
+// Diagnostic hook (not in astyle.h): device buffer of 64 rows of 20 u64 that -DASTYLE_STAMPS
+// builds of the block kernels accumulate into, one row per block launch (stamp_row): [0..15]
+// phase-cycle sums, [16] / [17] max / min wave lifetime, [18] / [19] first start / last end; NULL
+// disables.
+int ast_debug_stamps(void* dev_u64x20x64) {
     g_stamps = (unsigned long long*)dev_u64x20x64;
     g_stamp_row = 0;
     return 0;
@@ -784,70 +776,23 @@ int ast_create(const ast_cfg* cfg, int hip_device, ast_ctx** out) {
     if (e != hipSuccess) { delete x; return fail(AST_E_HIP, hipGetErrorString(e)); }
     decide_doop(cfg, x);
     const ast_cfg& c = *cfg;
-    const size_t BTC = (size_t)c.batch * c.T * C;
-    x->tstride = BTC + tensor_pad();
-    void* p;
-#define ALLOC(dst, bytes) do { if ((rc = dalloc(x, &p, (bytes), #dst))) { ast_destroy(x); return rc; } dst = (decltype(dst))p; } while (0)
+    x->tstride = (size_t)c.batch * c.T * C + tensor_pad();
     x->bf = c.precision == 1;
     x->split = c.precision == 2;
     x->esz = x->bf ? 2 : 4;
-    if (x->split) {
-        ALLOC(x->wtss, (size_t)NBLK_MAX * SBLK * 16);
-        (void)hipMemset(x->wtss, 0, (size_t)NBLK_MAX * SBLK * 16);
-        ALLOC(x->gmax_e, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4);
-        ALLOC(x->gmax_g, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4);
-    }
-    ALLOC(x->wts, W_TOTAL * 4);
-    (void)hipMemset(x->wts, 0, W_TOTAL * 4);
-    ALLOC(x->wtsb, (size_t)NBLK_MAX * BLKB_SZ * 2);
-    (void)hipMemset(x->wtsb, 0, (size_t)NBLK_MAX * BLKB_SZ * 2);
-    ALLOC(x->act, (size_t)(x->nblk + 1) * x->tstride * x->esz);
-    if (x->doop) {
-        ALLOC(x->dgrad, (size_t)(x->nblk + 1) * x->tstride * x->esz + d_pad());
-        x->dgrad = (char*)x->dgrad + d_pad();   // (x->allocs keeps the base for hipFree)
-    }
-    ALLOC(x->mu, (size_t)x->nblk * c.batch * c.T * 16);
-    ALLOC(x->me, (size_t)x->nblk * c.batch * c.T * 16);
-    ALLOC(x->chain[0], BTC * x->esz);
-    ALLOC(x->chain[1], BTC * x->esz);
-    const int fuse_u = fused_content_occ(x);   // (the Gram backward adds that tap's gradient itself)
-    for (int t = 0; t <= NBLK_MAX; ++t)
-        if ((x->tensor_has_direct_content[t] && !(fuse_u >= 0 && x->uid[fuse_u] == t)) || (t == 30 && (x->need_bott || c.with_encoding)))
-            ALLOC(x->cg_buf[t], BTC * x->esz);
-    if (x->need_bott) {
-        ALLOC(x->bott, (size_t)c.batch * c.T * 16 * 4);
-        ALLOC(x->gbott, (size_t)c.batch * c.T * 16 * 4);
-    }
-    ALLOC(x->gpart, x->gpart_elems * 4);
-    ALLOC(x->smat, x->smat_elems * 4);
-    if (c.gatys && x->bf) ALLOC(x->smatb, x->smat_elems * 2);
-    ALLOC(x->zero, 256);
-    (void)hipMemset(x->zero, 0, 256);
-    ALLOC(x->rflags, (size_t)c.batch * 4);
-    (void)hipMemset(x->rflags, 0, (size_t)c.batch * 4);
-    ALLOC(x->rflags_last, (size_t)c.batch * 4);
-    (void)hipMemset(x->rflags_last, 0, (size_t)c.batch * 4);
-    ALLOC(x->spart, (size_t)c.batch * C * 4);
     x->ncpart = (int)x->occ.size() * (c.T / CROWS);
-    ALLOC(x->cpart, (size_t)c.batch * x->ncpart * 4);
-    if (const int nf = stft_frames(c.T)) {
-        ALLOC(x->stft_tw, 1024 * 8);
-        ALLOC(x->stft_fpart, (size_t)c.batch * nf * 4);
-        ALLOC(x->stft_gfr, (size_t)c.batch * nf * 1024 * 4);
+    for (const Buf& b : buffer_table(c, x)) {
+        void* p;
+        if ((rc = dalloc(x, &p, b.bytes, b.name))) { ast_destroy(x); return rc; }
+        if (b.zero) (void)hipMemset(p, 0, b.bytes);
+        b.set(x, p, b.t);
+    }
+    if (x->dgrad) x->dgrad = (char*)x->dgrad + d_pad();   // (x->allocs keeps the base for hipFree)
+    if (x->stft_tw) {
         launch_stft_twiddles(x->stft_tw, nullptr);
         e = hipDeviceSynchronize();
         if (e != hipSuccess) { ast_destroy(x); return fail(AST_E_HIP, hipGetErrorString(e)); }
     }
-    ALLOC(x->anc_part, (size_t)c.batch * anchor_chunks(c.T) * 2 * 4);
-    ALLOC(x->anc_loss, (size_t)c.batch * 4);
-    if (c.with_encoding) {
-        const size_t BR = (size_t)c.batch * (c.T / 512);
-        ALLOC(x->enc, BR * 16 * 4);
-        ALLOC(x->enc_d, BR * 16 * 4);
-        ALLOC(x->enc_part, BR * 4);
-        ALLOC(x->enc_loss, (size_t)c.batch * 4);
-    }
-#undef ALLOC
     x->doop_tune = doop_env() < 0 && x->dgrad &&
                    (size_t)(x->nblk + 1) * x->tstride * x->esz >= ((size_t)4 << 30);
     *out = x;
@@ -879,129 +824,46 @@ int ast_set_weight(ast_ctx* x, const char* name, const float* host, size_t n) {
     if (s == "ae_startconv/biases") { if ((rc = need(C))) return rc; return put(B0_OFF, host, C); }
     if (s == "ae_bottleneck/W") { if ((rc = need(C * 16))) return rc; return put(WB_OFF, host, C * 16); }
     if (s == "ae_bottleneck/biases") { if ((rc = need(16))) return rc; return put(BB_OFF, host, 16); }
+    // a block's conv weights (ae_dilatedconv: W_d, 3 taps; ae_res: W_r, 1 tap): fp32 as given and
+    // transposed, and the bf16 and (split) fp16 fragments of pack.h
     int l = 0;
     char tail[32];
-    if (sscanf(name, "ae_dilatedconv_%d/%31s", &l, tail) == 2 && l >= 1 && l <= NBLK_MAX) {
-        const size_t base = BLK_OFF + (size_t)(l - 1) * BLK_SZ;
+    const bool isd = sscanf(name, "ae_dilatedconv_%d/%31s", &l, tail) == 2;
+    if ((isd || sscanf(name, "ae_res_%d/%31s", &l, tail) == 2) && l >= 1 && l <= NBLK_MAX) {
+        const int b = l - 1;
+        const size_t base = BLK_OFF + (size_t)b * BLK_SZ;
+        if (!strcmp(tail, "biases")) {
+            if ((rc = need(C))) return rc;
+            if (isd) x->bdm[b] = abs_max(host, C);
+            return put(base + (isd ? BD : BR), host, C);
+        }
         if (!strcmp(tail, "W")) {
-            if ((rc = need(3 * C * C))) return rc;
-            std::vector<float> tr(3 * C * C);
-            for (int k = 0; k < 3; ++k)
+            const int taps = isd ? 3 : 1;
+            const size_t cnt = (size_t)taps * C * C;
+            if ((rc = need(cnt))) return rc;
+            std::vector<float> tr(cnt);   // [tap][co][ci]
+            for (int k = 0; k < taps; ++k)
                 for (int ci = 0; ci < C; ++ci)
                     for (int co = 0; co < C; ++co)
                         tr[(size_t)k * C * C + co * C + ci] = host[(size_t)k * C * C + ci * C + co];
-            if ((rc = put(base + WD, host, 3 * C * C))) return rc;
-            if ((rc = put(base + WDT, tr.data(), 3 * C * C))) return rc;
-            std::vector<uint16_t> hb(6 * C * C), hf(3 * C * C), hg(3 * C * C);
-            for (size_t i = 0; i < 3 * C * C; ++i) { hb[i] = host_bf16(host[i]); hb[3 * C * C + i] = host_bf16(tr[i]); }
-            // forward fragments from W_d, backward fragments the same order from W_d^T
-            for (int k = 0; k < 3; ++k)
-                for (int q = 0; q < 4; ++q)
-                    for (int kb = 0; kb < 8; ++kb)
-                        for (int ln = 0; ln < 64; ++ln)
-                            for (int e = 0; e < 8; ++e) {
-                                const int ci = 16 * kb + 8 * (ln >> 5) + e, co = 32 * q + (ln & 31);
-                                const size_t o = ((((size_t)k * 4 + q) * 8 + kb) * 64 + ln) * 8 + e;
-                                hf[o] = hb[(size_t)k * C * C + ci * C + co];
-                                hg[o] = hb[3 * C * C + (size_t)k * C * C + ci * C + co];
-                            }
-            u16* dst = x->wtsb + (size_t)(l - 1) * BLKB_SZ;
-            HIPCHK(hipMemcpy(dst + WFB, hf.data(), 3 * C * C * 2, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dst + WBFB, hg.data(), 3 * C * C * 2, hipMemcpyHostToDevice));
-            if (x->split) {
-                // forward: element (w, tap, kb, hl, lane (m, h), e) = W_d[tap][16 kb + 8 h + e][32 w + m];
-                // backward: W_d[tap][32 w + m][16 kb + 8 h + e] (ASTYLE_MFMA16: frag_index)
-                const int k = weight_exp(host, 3 * C * C);
-                x->kd[l - 1] = k;
-                float nrm = 0.f;
-                for (int co = 0; co < C; ++co) {
-                    float sacc = 0.f;
-                    for (int i = 0; i < 3 * C; ++i) sacc += std::fabs(host[(size_t)i * C + co]);
-                    nrm = std::max(nrm, sacc);
-                }
-                x->wdn[l - 1] = nrm;
-                std::vector<uint16_t> f(3 * C * C * 2), g(3 * C * C * 2);
-                for (int w = 0; w < 4; ++w)
-                    for (int tp = 0; tp < 3; ++tp)
-                        for (int kb = 0; kb < 8; ++kb)
-                            for (int ln = 0; ln < 64; ++ln)
-                                for (int e = 0; e < 8; ++e) {
-                                    int kk, mm, kb2, mb2;
-                                    frag_index(mfma16_fwd(), kb, ln, e, w, kk, mm);
-                                    frag_index(mfma16_bwd(), kb, ln, e, w, kb2, mb2);
-                                    const size_t o = ((((size_t)(w * 3 + tp) * 8 + kb) * 2) * 64 + ln) * 8 + e;
-                                    split_half(host[(size_t)tp * C * C + kk * C + mm], k, f[o], f[o + 64 * 8]);
-                                    split_half(host[(size_t)tp * C * C + mb2 * C + kb2], k, g[o], g[o + 64 * 8]);
-                                }
-                uint4* ds = x->wtss + (size_t)(l - 1) * SBLK;
-                HIPCHK(hipMemcpy(ds + SWDF, f.data(), f.size() * 2, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(ds + SWDB, g.data(), g.size() * 2, hipMemcpyHostToDevice));
+            if ((rc = put(base + (isd ? WD : WR), host, cnt))) return rc;
+            if ((rc = put(base + (isd ? WDT : WRT), tr.data(), cnt))) return rc;
+            std::vector<uint16_t> f(2 * cnt), g(2 * cnt);   // forward, backward fragments
+            pack_bf16(host, taps, false, f.data());
+            pack_bf16(host, taps, true, g.data());
+            HIPCHK(hipMemcpy(blkwb(x, b) + (isd ? WFB : WRFB), f.data(), cnt * 2, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(blkwb(x, b) + (isd ? WBFB : WRBFB), g.data(), cnt * 2, hipMemcpyHostToDevice));
+            if (x->split) {   // each direction in the MFMA form of the kernel that reads it (ASTYLE_MFMA16)
+                (isd ? x->kd : x->kr)[b] = pack_split(host, taps, false, mfma16_fwd(), f.data());
+                pack_split(host, taps, true, mfma16_bwd(), g.data());
+                if (isd) x->wdn[b] = col_abs_sum_max(host, 3 * C);
+                else x->wrn[b] = row_abs_sum_max(host, C);
+                uint4* ds = x->wtss + (size_t)b * SBLK;
+                HIPCHK(hipMemcpy(ds + (isd ? SWDF : SWRF), f.data(), cnt * 4, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(ds + (isd ? SWDB : SWRB), g.data(), cnt * 4, hipMemcpyHostToDevice));
             }
             return 0;
         }
-        if (!strcmp(tail, "biases")) {
-            if ((rc = need(C))) return rc;
-            float m = 0.f;
-            for (int i = 0; i < C; ++i) m = std::max(m, std::fabs(host[i]));
-            x->bdm[l - 1] = m;
-            return put(base + BD, host, C);
-        }
-    }
-    if (sscanf(name, "ae_res_%d/%31s", &l, tail) == 2 && l >= 1 && l <= NBLK_MAX) {
-        const size_t base = BLK_OFF + (size_t)(l - 1) * BLK_SZ;
-        if (!strcmp(tail, "W")) {
-            if ((rc = need(C * C))) return rc;
-            std::vector<float> tr(C * C);
-            for (int ci = 0; ci < C; ++ci)
-                for (int co = 0; co < C; ++co) tr[co * C + ci] = host[ci * C + co];
-            if ((rc = put(base + WR, host, C * C))) return rc;
-            if ((rc = put(base + WRT, tr.data(), C * C))) return rc;
-            std::vector<uint16_t> hb(2 * C * C), hf(C * C), hg(C * C);
-            for (size_t i = 0; i < C * C; ++i) { hb[i] = host_bf16(host[i]); hb[C * C + i] = host_bf16(tr[i]); }
-            for (int q2 = 0; q2 < 4; ++q2)
-                for (int st = 0; st < 8; ++st)
-                    for (int ln = 0; ln < 64; ++ln)
-                        for (int e = 0; e < 8; ++e) {
-                            const int co = kperm(st, ln >> 5, e), co2 = 32 * q2 + (ln & 31);
-                            const size_t o = (((size_t)q2 * 8 + st) * 64 + ln) * 8 + e;
-                            hf[o] = hb[(size_t)co * C + co2];
-                            // backward: W_r[32 q + m][16 kb + 8 h + e] = W_r^T[16 kb + 8 h + e][32 q + m]
-                            hg[o] = hb[C * C + (size_t)(16 * st + 8 * (ln >> 5) + e) * C + 32 * q2 + (ln & 31)];
-                        }
-            u16* dst = x->wtsb + (size_t)(l - 1) * BLKB_SZ;
-            HIPCHK(hipMemcpy(dst + WRFB, hf.data(), C * C * 2, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dst + WRBFB, hg.data(), C * C * 2, hipMemcpyHostToDevice));
-            if (x->split) {
-                // forward: element (w, kb, hl, lane (m, h), e) = W_r[16 kb + 8 h + e][32 w + m];
-                // backward: W_r[32 w + m][16 kb + 8 h + e] (ASTYLE_MFMA16: frag_index)
-                const int k = weight_exp(host, C * C);
-                x->kr[l - 1] = k;
-                float nrm = 0.f;
-                for (int ci = 0; ci < C; ++ci) {
-                    float sacc = 0.f;
-                    for (int co = 0; co < C; ++co) sacc += std::fabs(host[(size_t)ci * C + co]);
-                    nrm = std::max(nrm, sacc);
-                }
-                x->wrn[l - 1] = nrm;
-                std::vector<uint16_t> f(C * C * 2), g(C * C * 2);
-                for (int w = 0; w < 4; ++w)
-                    for (int kb = 0; kb < 8; ++kb)
-                        for (int ln = 0; ln < 64; ++ln)
-                            for (int e = 0; e < 8; ++e) {
-                                int kk, mm, kb2, mb2;
-                                frag_index(mfma16_fwd(), kb, ln, e, w, kk, mm);
-                                frag_index(mfma16_bwd(), kb, ln, e, w, kb2, mb2);
-                                const size_t o = ((((size_t)w * 8 + kb) * 2) * 64 + ln) * 8 + e;
-                                split_half(host[(size_t)kk * C + mm], k, f[o], f[o + 64 * 8]);
-                                split_half(host[(size_t)mb2 * C + kb2], k, g[o], g[o + 64 * 8]);
-                            }
-                uint4* ds = x->wtss + (size_t)(l - 1) * SBLK;
-                HIPCHK(hipMemcpy(ds + SWRF, f.data(), f.size() * 2, hipMemcpyHostToDevice));
-                HIPCHK(hipMemcpy(ds + SWRB, g.data(), g.size() * 2, hipMemcpyHostToDevice));
-            }
-            return 0;
-        }
-        if (!strcmp(tail, "biases")) { if ((rc = need(C))) return rc; return put(base + BR, host, C); }
     }
     return fail(AST_E_NAME, "not an encoder variable: " + s);
 }
@@ -1054,7 +916,7 @@ int ast_embeds(ast_ctx* x, const float* xd, float* emb_c, float* emb_s, void* st
     }
     if (emb_s && c.gatys) {
         GatysArgs g = gatys_args(x);
-        launch_gatys_fwd(g, x->split ? 2 : (x->bf ? 1 : 0), s);
+        launch_gatys_fwd(g, c.precision, s);
         GatysStyleArgs a = gatys_style_args(x);
         a.embs = emb_s;
         launch_style_gatys(a, s);
@@ -1216,11 +1078,9 @@ static int loss_grad_front(ast_ctx* x, const float* xd, hipStream_t s) {
     const int ntop = bwd_top(x);
     // style (methods.py:62-76, 118-119)
     tmark(x, s);
-    bool& top_max_done = x->lg_top_max_done;   // split: the Gram bwd recorded the top tensor's per-clip max
-    top_max_done = false;
     if (c.gatys) {
         GatysArgs g = gatys_args(x);
-        launch_gatys_fwd(g, x->split ? 2 : (x->bf ? 1 : 0), s);
+        launch_gatys_fwd(g, c.precision, s);
         tmark(x, s);
         GatysStyleArgs sa = gatys_style_args(x);
         sa.phi = x->phi_s;
@@ -1228,21 +1088,9 @@ static int loss_grad_front(ast_ctx* x, const float* xd, hipStream_t s) {
         sa.smat = x->smat; sa.smatb = x->smatb; sa.spart = x->spart;
         launch_style_gatys(sa, s);
         tmark(x, s);
-        if (x->split && x->tensor_in_style[ntop]) {   // the chain's first max |tot| inside the Gatys bwd
-            for (int u = 0; u < x->nu; ++u) if (x->uid[u] == ntop) g.top_u = u;
-            g.gmax_top = x->gmax_g + (size_t)ntop * c.batch * GCLIP_W;
-            launch_zero32(x->gmax_g, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4, s, 2);
-            top_max_done = g.top_u >= 0;
-        }
-        if (fuse_u >= 0) {   // the split Gatys backward adds the content tap (one slot per 512-row tile)
-            const Occ& o = x->occ[0];
-            g.cg[fuse_u] = nullptr;
-            g.cont_u = fuse_u;
-            g.cont_phi = x->phi_c; g.cont_phi_bstride = x->phi_c_shared ? 0 : (size_t)c.T * x->ncc;
-            g.cont_ncc = x->ncc; g.cont_off = o.off; g.cont_ncol = o.ncol; g.cont_coef = ccoef;
-            g.cont_part = x->cpart; g.cont_pstride = (size_t)x->ncpart;
-        }
-        if ((rc = timed_gram_bwd(x, [&](void* dst) { GatysArgs gg = g; gg.actw = dst; launch_gatys_bwd(gg, x->split ? 2 : (x->bf ? 1 : 0), s); }, s)))
+        x->lg_top_max_done = set_top_max(x, g, ntop, s);
+        if (fuse_u >= 0) set_fused_content(x, g, fuse_u, ccoef);
+        if ((rc = timed_gram_bwd(x, [&](void* dst) { GatysArgs gg = g; gg.actw = dst; launch_gatys_bwd(gg, c.precision, s); }, s)))
             return rc;
     } else {
         GramArgs g = gram_args(x);
@@ -1254,20 +1102,8 @@ static int loss_grad_front(ast_ctx* x, const float* xd, hipStream_t s) {
         sa.smat = x->smat; sa.spart = x->spart;
         launch_style_ours(sa, s);
         tmark(x, s);
-        if (x->split && x->tensor_in_style[ntop]) {   // the chain's first max |tot| inside the Gram bwd
-            for (int u = 0; u < x->nu; ++u) if (x->uid[u] == ntop) g.top_u = u;
-            g.gmax_top = x->gmax_g + (size_t)ntop * c.batch * GCLIP_W;
-            launch_zero32(x->gmax_g, (size_t)(NBLK_MAX + 1) * c.batch * GCLIP_W * 4, s, 2);
-            top_max_done = g.top_u >= 0;
-        }
-        if (fuse_u >= 0) {
-            const Occ& o = x->occ[0];
-            g.cg[fuse_u] = nullptr;
-            g.cont_u = fuse_u;
-            g.cont_phi = x->phi_c; g.cont_phi_bstride = x->phi_c_shared ? 0 : (size_t)c.T * x->ncc;
-            g.cont_ncc = x->ncc; g.cont_off = o.off; g.cont_ncol = o.ncol; g.cont_coef = ccoef;
-            g.cont_part = x->cpart; g.cont_pstride = (size_t)x->ncpart;
-        }
+        x->lg_top_max_done = set_top_max(x, g, ntop, s);
+        if (fuse_u >= 0) set_fused_content(x, g, fuse_u, ccoef);
         g.nchunk = x->nchunk_b;
         if ((rc = timed_gram_bwd(x, [&](void* dst) { GramArgs gg = g; gg.actw = dst; launch_gram_bwd_any(x, gg, s); }, s)))
             return rc;
@@ -1351,12 +1187,9 @@ static int loss_grad_back(ast_ctx* x, const float* xd, float* grad, float* parts
     else if (x->bf) launch_startconv_bwd((const u16*)x->chain[0], grad, x->wts + W0_OFF, c.batch, c.T, s);
     else launch_startconv_bwd((const float*)x->chain[0], grad, x->wts + W0_OFF, c.batch, c.T, s);
     const int nb = std::min(c.nb_channels, C);
-    if (c.gatys)
-        launch_finalize(parts, x->cpart, x->ncpart, 10.0f / ((float)c.T * (float)x->ncc), x->spart,
-                        x->nu, 1e3f / (float)(x->L * C * C), c.lambd, c.batch, s);
-    else
-        launch_finalize(parts, x->cpart, x->ncpart, 10.0f / ((float)c.T * (float)x->ncc), x->spart,
-                        C, 1e3f / (float)(nb * x->L * x->L), c.lambd, c.batch, s);
+    launch_finalize(parts, x->cpart, x->ncpart, 10.0f / ((float)c.T * (float)x->ncc), x->spart,
+                    c.gatys ? x->nu : C, 1e3f / (float)(c.gatys ? x->L * C * C : nb * x->L * x->L),
+                    c.lambd, c.batch, s);
     // STFT regulariser (methods.py:121-125): TF evaluates it whatever gamma is, so parts[3]
     // always holds it; its gradient enters grad only through gamma
     launch_stft_reg(xd, x->stft_tw, x->stft_fpart, x->stft_gfr, grad, parts, c.gamma, c.batch,

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "knob.h"   // env_int / env_flag: the one reader of the ASTYLE_* tuning knobs
 
 namespace ast {
 
@@ -138,8 +139,8 @@ struct BwdArgs {
 struct FwdArgsC {
     unsigned long long* stamps;            // diagnostic builds (-DASTYLE_STAMPS) only
     const u16* ein; u16* eout;
-    const u16* wf;         // [3 taps][4 q][8 kb][64 lanes][8] W_d^T A fragments
-    const u16* wrf;        // [4 q2][8 s][64][8] W_r^T A fragments, K in accumulator order
+    const u16* wf;         // W_d A fragments, K = input channel (pack.h: WFB)
+    const u16* wrf;        // W_r A fragments, K in accumulator order (pack.h: WRFB)
     const float* bd; const float* br;
     uint16_t* mu;          // [B*T][2 h][4 q] u > 0 bits, this layer's positions
     uint16_t* me_next;     // [B*T][2][4] e_{l+1} > 0 bits, the next layer's positions (or null)
@@ -154,9 +155,8 @@ struct BwdArgsC {
     const u16* tin;        // d loss / d e_{l+1} incl. its direct term (chain, or D_{l+1} at the top)
     const u16* dadd;       // D_l, the direct loss gradient of e_l (or null)
     u16* gout;             // d loss / d e_l incl. D_l
-    const u16* wbf;        // [3 taps][4 q][8 kb][64 lanes][8] W_d A fragments:
-                           //   lane (m, h) element e = W_d[tap][ci = 32 q + m][co = 16 kb + 8 h + e]
-    const u16* wrb;        // [4 q][8 kb][64][8] W_r A fragments: W_r[co = 32 q + m][o = 16 kb + 8 h + e]
+    const u16* wbf;        // W_d A fragments, K = output channel (pack.h: WBFB)
+    const u16* wrb;        // W_r A fragments, K = output channel (pack.h: WRBFB)
     const uint16_t* mu;    // [B*T][2 h][4 q] u > 0 bits, this layer's positions
     const uint16_t* me;    // [B*T][2][4] e_l > 0 bits, this layer's positions
     const u16* zero;       // >= 256 zero bytes
@@ -164,17 +164,10 @@ struct BwdArgsC {
 };
 
 // split-fp16 block kernels (precision 2: block_fwd_split.hip, block_bwd_split.hip).  Weight
-// fragments are fp16 halves of W 2^k (k = kd / kr per block, host-chosen), 8 halves per lane:
-//   wdf [4 w][3 tap][8 kb][2 hl][64 lanes]: lane (m, h) element e = W_d[tap][16 kb + 8 h + e][32 w + m]
-//   wrf [4 w][8 kb][2 hl][64]:                                     W_r[16 kb + 8 h + e][32 w + m]
-//   wrb [4 w][8 kb][2 hl][64]:                                     W_r[32 w + m][16 kb + 8 h + e]
-//   wdb [4 w][3 tap][8 kb][2 hl][64]:                              W_d[tap][32 w + m][16 kb + 8 h + e]
-// For the 16x16x32 kernels (k_block_fwd_s16 of block_fwd_split.hip, k_block_bwd_s16 of
-// block_bwd_split.hip; ASTYLE_MFMA16
-// picks the form per direction, the default 2: the backward on 16x16x32, the forward on 32x32x16)
-// a direction's arrays hold 16x16x32 A fragments, slot s = 2 kb + rb (K block kb of 32, row block rb), lane (i, q) = (lane & 15, lane >> 4):
-//   wdf: W_d[tap][32 kb + 8 q + e][32 w + 16 rb + i]     wrf: W_r[32 kb + 8 q + e][32 w + 16 rb + i]
-//   wrb: W_r[32 w + 16 rb + i][32 kb + 8 q + e]          wdb: W_d[tap][32 w + 16 rb + i][32 kb + 8 q + e]
+// fragments wdf / wrf / wrb / wdb are fp16 halves of W 2^k (k = kd / kr per block, host-chosen),
+// 8 halves per lane, in 32x32x16 A-fragment order or, for the 16x16x32 kernels (k_block_fwd_s16,
+// k_block_bwd_s16), in 16x16x32 order; ASTYLE_MFMA16 picks the form per direction (default 2: the
+// backward on 16x16x32, the forward on 32x32x16).  The layouts (SWDF, SWRF, SWRB, SWDB): pack.h.
 // gmax_*: per clip max |x| of a tensor as float bits (atomic max of the non-negative bit pattern),
 // in GSLOTS slots per clip, one 128-B line each ([level][clip][slot][32 words], word 0 used): a
 // writer takes slot blockIdx.x % GSLOTS (one per XCD under round-robin placement), a reader the
@@ -323,11 +316,10 @@ struct ContentArgs {
     int B, T;
 };
 
-// launchers (encoder.hip / gram.hip / optim.hip)
+// launchers (encoder.hip, the block_* / gram* files)
 template <typename S>
 void launch_startconv_fwd(const float* x, S* e0, const float* w0, const float* b0,
-                          int B, int T, hipStream_t s, uint16_t* me0 = nullptr,
-                          unsigned* gmax = nullptr);
+                          int B, int T, hipStream_t s, uint16_t* me0 = nullptr);
 // split mode: only the e_0 > 0 words and the per-clip max |e_0| (block 0 recomputes e_0)
 void launch_startconv_masks(const float* x, const float* w0, const float* b0, int B, int T,
                             hipStream_t s, uint16_t* me0, unsigned* gmax);

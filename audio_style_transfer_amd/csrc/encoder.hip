@@ -236,8 +236,7 @@ __global__ void __launch_bounds__(256) k_startconv_fwd(const float* __restrict__
                                                        S* __restrict__ e0,
                                                        const float* __restrict__ w0,
                                                        const float* __restrict__ b0, int B,
-                                                       int T, uint16_t* __restrict__ me0,
-                                                       unsigned* __restrict__ gmax) {
+                                                       int T, uint16_t* __restrict__ me0) {
     // SFR rows per workgroup, 16 lanes per row; this lane's 8 channels' weights load once
     const int m = threadIdx.x & 15;
     float wk[3][8], bk[8];
@@ -246,9 +245,7 @@ __global__ void __launch_bounds__(256) k_startconv_fwd(const float* __restrict__
         wk[0][j] = w0[m * 8 + j]; wk[1][j] = w0[C + m * 8 + j]; wk[2][j] = w0[2 * C + m * 8 + j];
         bk[j] = b0[m * 8 + j];
     }
-    float amax = 0.f;
-    // clip-interleaved block order (block i: clip i mod B, row chunk i / B): concurrently running
-    // workgroups belong to different clips, so their max atomics do not pile onto one word
+    // clip-interleaved block order (block i: clip i mod B, row chunk i / B), as k_startconv_masks
     const int nper = T / SFR;
     const size_t lb = (size_t)(blockIdx.x % B) * nper + blockIdx.x / B;
     // the workgroup's SFR samples and their two neighbours, one coalesced load (zero past the clip)
@@ -290,10 +287,6 @@ __global__ void __launch_bounds__(256) k_startconv_fwd(const float* __restrict__
                 pos[2 * k + 1] = (int)p[k] >= 0x10000;
             }
         }
-        if (gmax) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(o[j]));
-        }
         if (me0) {
             // e_0 > 0 bits for block 0's backward (dilation 1: position = time) in the MFMA
             // accumulator layout (common.h): channel 32 Q + 8 g + 4 h + j is element
@@ -318,12 +311,6 @@ __global__ void __launch_bounds__(256) k_startconv_fwd(const float* __restrict__
             if (m == 0)
                 *reinterpret_cast<uint4*>(me0 + rowi * 8) = make_uint4(wd[0], f0, wd[1], f1);
         }
-    }
-    if (gmax) {
-        // max |e_0| of the workgroup's rows (one clip: T is a multiple of SFR) -> the clip's max
-        amax = wave_max_f(amax);
-        if ((threadIdx.x & 63) == 0)
-            atomicMax(gmax + blockIdx.x % B, __float_as_uint(amax));
     }
 }
 
@@ -504,9 +491,9 @@ void launch_block_bwd(const BwdArgs& a, hipStream_t s) {
 }
 template <typename S>
 void launch_startconv_fwd(const float* x, S* e0, const float* w0, const float* b0, int B, int T,
-                          hipStream_t s, uint16_t* me0, unsigned* gmax) {
+                          hipStream_t s, uint16_t* me0) {
     hipLaunchKernelGGL(k_startconv_fwd<S>, dim3((unsigned)((size_t)B * T / SFR)), dim3(256), 0, s, x,
-                       e0, w0, b0, B, T, me0, gmax);
+                       e0, w0, b0, B, T, me0);
 }
 void launch_startconv_masks(const float* x, const float* w0, const float* b0, int B, int T,
                             hipStream_t s, uint16_t* me0, unsigned* gmax) {
@@ -548,8 +535,7 @@ void launch_zero32(void* p, size_t bytes, hipStream_t s, int site) {
     // tools-only build (ASTYLE_VARIANT=memset ASTYLE_DEFS=-DASTYLE_MEMSET_CLEARS): the round-4
     // hipMemsetAsync clears, for tools/determinism2.py (graph replays); env
     // ASTYLE_MEMSET_SITES=<bit mask of sites> keeps the other sites on k_zero32 (default: all)
-    static int mask = -1;
-    if (mask < 0) { const char* e = getenv("ASTYLE_MEMSET_SITES"); mask = e ? atoi(e) : 0xff; }
+    static const int mask = (int)env_int("ASTYLE_MEMSET_SITES", 0xff, INT_MIN, INT_MAX);
     if (site < 0 || ((mask >> site) & 1)) {
         (void)hipMemsetAsync(p, 0, bytes, s);
         return;
@@ -561,8 +547,8 @@ void launch_zero32(void* p, size_t bytes, hipStream_t s, int site) {
 void launch_to_f32(const u16* src, float* dst, size_t n, hipStream_t s) {
     hipLaunchKernelGGL(k_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, n);
 }
-template void launch_startconv_fwd<float>(const float*, float*, const float*, const float*, int, int, hipStream_t, uint16_t*, unsigned*);
-template void launch_startconv_fwd<u16>(const float*, u16*, const float*, const float*, int, int, hipStream_t, uint16_t*, unsigned*);
+template void launch_startconv_fwd<float>(const float*, float*, const float*, const float*, int, int, hipStream_t, uint16_t*);
+template void launch_startconv_fwd<u16>(const float*, u16*, const float*, const float*, int, int, hipStream_t, uint16_t*);
 template void launch_startconv_bwd<float>(const float*, float*, const float*, int, int, hipStream_t);
 template void launch_startconv_bwd<u16>(const u16*, float*, const float*, int, int, hipStream_t);
 template void launch_bottleneck_fwd<float>(const float*, float*, const float*, const float*, int, int, hipStream_t);

@@ -654,8 +654,8 @@ void launch_gatys_fwd(const GatysArgs& a, int precision, hipStream_t s) {
     const dim3 g(a.B * a.nu * a.nchunk);
     if (precision == 1) hipLaunchKernelGGL(k_gatys_fwd_bf16, g, dim3(256), 0, s, a);
     else if (precision == 2) {   // ASTYLE_GATYS_STAGES=3: three load stages in flight (A/B; default 2)
-        const char* e = getenv("ASTYLE_GATYS_STAGES");
-        if (e && atoi(e) == 3) hipLaunchKernelGGL(k_gatys_fwd_s<3>, g, dim3(256), 0, s, a);
+        static const int stages = (int)env_int("ASTYLE_GATYS_STAGES", 2, {2, 3});
+        if (stages == 3) hipLaunchKernelGGL(k_gatys_fwd_s<3>, g, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_gatys_fwd_s<2>, g, dim3(256), 0, s, a);
     }
     else hipLaunchKernelGGL(k_gatys_fwd_f32, g, dim3(256), 0, s, a);

@@ -746,13 +746,11 @@ __global__ void __launch_bounds__(GWT) k_gram_bwd_f(GramArgs a) {
 }  // namespace
 
 static int gram_bwd_stages() {   // ASTYLE_GRAM_BWD_STAGES=2 / 3 (A/B; default 2 until measured)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ASTYLE_GRAM_BWD_STAGES"); v = e ? atoi(e) : 2; if (v != 3) v = 2; }
+    static const int v = (int)env_int("ASTYLE_GRAM_BWD_STAGES", 2, {2, 3});
     return v;
 }
 static int gram_stages() {   // ASTYLE_GRAM_STAGES=2 / 3 (A/B; default 3)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ASTYLE_GRAM_STAGES"); v = e ? atoi(e) : 3; if (v != 2) v = 3; }
+    static const int v = (int)env_int("ASTYLE_GRAM_STAGES", 3, {2, 3});
     return v;
 }
 void launch_gram_fwd_s(const GramArgs& a, hipStream_t s) {
@@ -763,18 +761,18 @@ void launch_gram_fwd_s(const GramArgs& a, hipStream_t s) {
         // one clip: 4 channels per workgroup (twice the workgroups) and 3 fills in flight; more
         // clips: 8 and 2 (round 6, one clip: Gram forward 0.343 -> 0.233 ms, same bits,
         // profiles/r6_diag/fewclip_ab.txt).  A/B knobs: ASTYLE_GRAM_FWDN_NC (4 / 8),
-        // ASTYLE_GRAM_FWDN_FILLS (2 / 3)
-        static int nfl = -1, ncw = -1;
-        if (nfl < 0) { const char* e = getenv("ASTYLE_GRAM_FWDN_FILLS"); nfl = e ? atoi(e) : 0; }
-        if (ncw < 0) { const char* e = getenv("ASTYLE_GRAM_FWDN_NC"); ncw = e ? atoi(e) : 0; }
+        // ASTYLE_GRAM_FWDN_FILLS (2 / 3); any other value is as unset (the grid is sized by nc, and
+        // only the 4- and 8-channel kernels exist)
+        static const int nfl = (int)env_int("ASTYLE_GRAM_FWDN_FILLS", 0, {2, 3});
+        static const int ncw = (int)env_int("ASTYLE_GRAM_FWDN_NC", 0, {4, 8});
         const int nc = ncw ? ncw : (a.B == 1 ? 4 : 8);
         const int nf = nfl ? nfl : (nc == 4 ? 3 : 2);
         const dim3 grid(a.B * a.nchunk * (C / nc));
         if (nc == 4) {
-            if (nf <= 2) hipLaunchKernelGGL((k_gram_fwd_n<2, 4>), grid, dim3(256), 0, s, a);
+            if (nf == 2) hipLaunchKernelGGL((k_gram_fwd_n<2, 4>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((k_gram_fwd_n<3, 4>), grid, dim3(256), 0, s, a);
         } else {
-            if (nf <= 2) hipLaunchKernelGGL((k_gram_fwd_n<2, 8>), grid, dim3(GWT), 0, s, a);
+            if (nf == 2) hipLaunchKernelGGL((k_gram_fwd_n<2, 8>), grid, dim3(GWT), 0, s, a);
             else hipLaunchKernelGGL((k_gram_fwd_n<3, 8>), grid, dim3(GWT), 0, s, a);
         }
         return;
@@ -808,9 +806,8 @@ static int gram_bwd_h_chunks(int B, int T) {
     return d;
 }
 static bool gram_bwd_half() {   // ASTYLE_GRAM_BWD_H=0: the 32-channel kernel (A/B)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("ASTYLE_GRAM_BWD_H"); v = e ? (atoi(e) != 0) : 1; }
-    return v != 0;
+    static const bool on = env_flag("ASTYLE_GRAM_BWD_H", 1) != 0;
+    return on;
 }
 bool gram_bwd_s_half(const GramArgs& a) {   // (a content-gradient buffer: the 32-channel kernel)
     if (!gram_bwd_half() || a.T % HSLOT) return false;

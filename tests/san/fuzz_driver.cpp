@@ -8,6 +8,13 @@
 //   cfg <seed> <n>     n seeded random ast_cfg values (in and out of range) through
 //                      ast_workspace_bytes, the validation / sizing of ast_create
 //                      (methods.py:44-77); one line per config
+//   pack <seed> <out>  the weight-fragment packers of csrc/pack.h on seeded normal W_d [3][128][128]
+//                      and W_r [128][128], as drawn and scaled by 1e-4 and 1e3 (the exponent
+//                      moves): per case the two inputs, then each tensor's split fragments with
+//                      their exponent in both MFMA forms and directions, then its bf16 fragments
+//                      in both directions, raw, to <out> (tests/test_pack_cpu.py reads it)
+//   knob               env_int / env_flag of csrc/knob.h: a value outside a knob's domain is the
+//                      default
 // A sanitizer report aborts the process (halt_on_error, -fno-sanitize-recover), so a clean exit
 // means no report.
 #include <cstdint>
@@ -19,6 +26,8 @@
 #include <vector>
 
 #include "../../include/astyle.h"
+#include "../../audio_style_transfer_amd/csrc/knob.h"
+#include "../../audio_style_transfer_amd/csrc/pack.h"
 
 static int run_ckpt(const char* list) {
     std::ifstream in(list);
@@ -89,9 +98,80 @@ static int run_cfg(unsigned seed, int n) {
     return 0;
 }
 
+static int run_pack(unsigned seed, const char* out) {
+    using namespace ast;
+    std::FILE* f = std::fopen(out, "wb");
+    if (!f) return 3;
+    auto put = [&](const void* p, size_t bytes) { return std::fwrite(p, 1, bytes, f) == bytes; };
+    std::mt19937 rng(seed);
+    std::normal_distribution<float> nd(0.f, 1.f);
+    std::vector<float> base(4 * WC * WC);   // W_d [3][WC][WC], then W_r [WC][WC]
+    for (float& v : base) v = nd(rng);
+    bool ok = true;
+    for (const float scale : {1.f, 1e-4f, 1e3f}) {
+        std::vector<float> w(base);
+        for (float& v : w) v *= scale;
+        ok = ok && put(w.data(), w.size() * 4);
+        const float* W[2] = {w.data(), w.data() + 3 * WC * WC};
+        const int taps[2] = {3, 1};
+        for (int t = 0; t < 2; ++t)
+            for (int m16 = 0; m16 < 2; ++m16)
+                for (int bwd = 0; bwd < 2; ++bwd) {
+                    std::vector<uint16_t> frag((size_t)taps[t] * WC * WC * 2);
+                    const int32_t k = pack_split(W[t], taps[t], bwd != 0, m16 != 0, frag.data());
+                    ok = ok && put(&k, 4) && put(frag.data(), frag.size() * 2);
+                }
+        for (int t = 0; t < 2; ++t)
+            for (int bwd = 0; bwd < 2; ++bwd) {
+                std::vector<uint16_t> frag((size_t)taps[t] * WC * WC);
+                pack_bf16(W[t], taps[t], bwd != 0, frag.data());
+                ok = ok && put(frag.data(), frag.size() * 2);
+            }
+    }
+    return std::fclose(f) == 0 && ok ? 0 : 3;
+}
+
+static int run_knob() {
+    using namespace ast;
+    const char* n = "ASTYLE_TEST_KNOB";
+    int bad = 0;
+    auto expect = [&](const char* val, long got, long want) {
+        if (got != want) { std::printf("BAD %s=%s: %ld, expected %ld\n", n, val ? val : "(unset)", got, want); ++bad; }
+    };
+    unsetenv(n);
+    expect(nullptr, env_int(n, 0, {4, 8}), 0);
+    expect(nullptr, env_int(n, 2, 0, 3), 2);
+    expect(nullptr, env_flag(n, -1), -1);
+    for (const char* v : {"2", "0", "-4", "16", "x", ""}) {   // outside {4, 8}: as unset
+        setenv(n, v, 1);
+        expect(v, env_int(n, 0, {4, 8}), 0);
+    }
+    for (const char* v : {"4", "8"}) {
+        setenv(n, v, 1);
+        expect(v, env_int(n, 0, {4, 8}), std::atol(v));
+    }
+    setenv(n, "3", 1);
+    expect("3", env_int(n, 2, 0, 3), 3);
+    expect("3", env_int(n, 0, {2, 3}), 3);
+    expect("3", env_flag(n, -1), 1);
+    setenv(n, "4", 1);
+    expect("4", env_int(n, 2, 0, 3), 2);
+    expect("4", env_int(n, 0, {2, 3}), 0);
+    setenv(n, "-1", 1);
+    expect("-1", env_int(n, 2, 0, 3), 2);
+    expect("-1", env_int(n, 7), -1);
+    setenv(n, "0", 1);
+    expect("0", env_flag(n, 1), 0);
+    unsetenv(n);
+    std::printf("%d\n", bad);
+    return bad ? 3 : 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "ckpt")) return run_ckpt(argv[2]);
     if (argc >= 4 && !std::strcmp(argv[1], "cfg")) return run_cfg((unsigned)std::atoi(argv[2]), std::atoi(argv[3]));
-    std::fprintf(stderr, "usage: fuzz_driver ckpt <list> | cfg <seed> <n>\n");
+    if (argc >= 4 && !std::strcmp(argv[1], "pack")) return run_pack((unsigned)std::atoi(argv[2]), argv[3]);
+    if (argc >= 2 && !std::strcmp(argv[1], "knob")) return run_knob();
+    std::fprintf(stderr, "usage: fuzz_driver ckpt <list> | cfg <seed> <n> | pack <seed> <out> | knob\n");
     return 2;
 }
